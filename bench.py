@@ -10,6 +10,23 @@ in the reference's per-iteration timing methodology (setup excluded,
 reported separately).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the
+inputs and the session, runs the W warmup steps, times the K steps, writes
+the outputs (``--dump-outputs DIR``) and prints the result line.  ``--full``
+adds what takes runs of its own: the reference CPU path timed on this host
+(``cpu_baseline``), the per-kernel HIP-event pass with the roofline of every
+sweep (and the PMC traffic that prices it), and, for a workload solved to
+tolerance, the second, profiled solve.
+
+``--dump-outputs DIR`` writes what the timed path returned after its last
+timed step (``Session.result()``: the iterate X, the iteration count and the
+recorded Obj / Dif where the workload records them) as ``DIR/<name>.npy``,
+float32 or float64, 64 MB at most in all: a larger X is written as a fixed,
+seeded sample of its entries (``X.npy`` the values, ``X_index.npy`` where
+they sit).  The inputs are generated deterministically, so two builds run
+with the same arguments are compared output for output.
 
 N > 1 (launched by torch.distributed.run, one process per GPU): every rank
 owns a z-slab of the graph (1-D vertex-range partition, RCCL halo exchange,
@@ -20,12 +37,13 @@ updates / max-over-ranks time.  The ranks bootstrap over a gloo (host)
 process group; the one RCCL communicator of the process is the library's
 (halo exchanges, scalar all-reduces, the max-over-ranks timing reduction).
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel and
-of every sweep beside it (HIP events on the session stream over the timed
-region; SURVEY.md §8(d)'s bytes split per sweep as tools/workloads.py states;
-PMC traffic from profiles/pmc/<workload>.json), the whole iteration's
-fraction, and the reference CPU path timed on this host (bounded sample, its
-own process, before this process touches the GPU).
+Prints ONE JSON line (rank 0) with the whole iteration's fraction of the HBM
+roofline and, with ``--full``, the roofline of the dominant kernel and of
+every sweep beside it (HIP events on the session stream in a profiled pass of
+the same length; SURVEY.md §8(d)'s bytes split per sweep as
+tools/workloads.py states; PMC traffic from profiles/pmc/<workload>.json)
+and the reference CPU path timed on this host (bounded sample, its own
+process, before this process touches the GPU).
 `--workload c1..c5` selects the other BASELINE.json configs
 (tools/workloads.py), measured for DESIGN.md; the driver's line is the
 default headline.
@@ -43,6 +61,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files of a run together
+DUMP_SEED = 20240611           # the sample of an output larger than that
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 CPU_PAIRS = 5          # CPU baseline: paired (T(k0), T(k1)) estimates, median reported
 CORE_GBS = 25.0        # one host core's streaming rate, upper bound (baseline floor)
@@ -222,6 +242,28 @@ def pmc_summary(wl, E):
         return None, "no PMC summary (%s)" % type(ex).__name__
 
 
+def dump_outputs(path, res, rank, world):
+    """--dump-outputs: what Session.result() returned after the last timed
+    step, one .npy per array (float32 / float64), every rank its own files,
+    DUMP_BYTES at most over all of them"""
+    os.makedirs(path, exist_ok=True)
+    X, it, Obj, Dif = res
+    tag = "" if world == 1 else "_rank%d" % rank
+    out = {"iterations": np.array([it], np.float64)}
+    for k, a in (("Obj", Obj), ("Dif", Dif)):
+        if a is not None:  # recorded per iteration: a few kB
+            out[k] = np.ascontiguousarray(a[: max(it, 1) + (k == "Obj")])
+    budget = DUMP_BYTES // world - sum(a.nbytes for a in out.values()) - 4096
+    if X.nbytes <= budget:
+        out["X"] = X
+    else:  # the same entries in every run: a seeded draw, 12 bytes each with its index
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, X.size, budget // 12))
+        out["X"], out["X_index"] = X[idx], idx.astype(np.float64)
+    for k, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(path, k + tag + ".npy"), a)
+
+
 # every launch of a kernel family once per iteration: a partitioned session's
 # boundary launches (edge_sweep_b, vertex_sweep_b) complete the interior ones
 FAMILIES = {"edge_sweep": ("edge_sweep", "edge_sweep_b"),
@@ -239,12 +281,20 @@ def main():
     ap.add_argument("--workload", default="headline")
     ap.add_argument("--scaling", default="strong", choices=("strong", "weak"),
                     help="N > 1: split the configuration's graph (strong) or one slab per GPU (weak)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baseline, the per-kernel "
+                         "event pass and its roofline, the profiled solve of a workload timed "
+                         "to tolerance")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last timed step as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--host-inputs", action="store_true",
                     help="hand the session host arrays (pinned for their copies during the "
                          "setup) instead of device-resident inputs (A/B runs)")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="time the steps without per-kernel HIP events (A/B runs)")
+                    help="--full without the per-kernel HIP event pass (A/B runs)")
     ap.add_argument("--dist-selftest", action="store_true",
                     help="one rank through the whole distributed path (gloo bootstrap, RCCL "
                          "communicator, partitioned session): a one-GPU rehearsal of N > 1")
@@ -260,6 +310,8 @@ def main():
         return
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        sys.exit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not launched per rank: start one process per GPU as a CHILD (this
         # process never touches the GPU) and exit with its status
@@ -282,11 +334,10 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dist_on = world > 1 or args.dist_selftest
-    # CPU baseline first, in its own process, before this process touches the GPU
+    # CPU baseline (--full) first, in its own process, before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and wl.name in ("headline", "headline_conv", "c1", "c2", "c3",
-                                                 "c4", "c5") and \
-            not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and \
+            wl.name in ("headline", "headline_conv", "c1", "c2", "c3", "c4", "c5"):
         cpu = run_cpu_baseline(args)
 
     import torch
@@ -344,8 +395,8 @@ def main():
     # the timed steps run unprofiled, so the session replays its captured
     # chunks (one hipGraph launch per 32 iterations; RCCL partitions with the
     # pull, sweeps and push inside): the production launch path.  The kernel
-    # means come from a second, profiled pass of the same length.
-    post_events = not converge and not args.no_kernel_events
+    # means come from a second, profiled pass of the same length (--full).
+    post_events = args.full and not converge and not args.no_kernel_events
     itMax = steps if converge else warm + steps + (steps if post_events else 0)
     t = time.perf_counter()
     sess = pfdr.Session(wl.kind, wl.dtype, V, E, itMax=itMax, **kw, **dist_kw)
@@ -385,24 +436,26 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         el_max, E_all = float(tmax[0]), int(tsum[0])
+    res = sess.result()  # what the timed path computed: the state after its last timed step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
     if post_events:
         sess.profile(True, period=period, only=timed)
         sess.run(steps)
         torch.cuda.synchronize()
         barrier()
-    if converge:
-        res_timed = sess.result()
+    if converge and args.full:
         sess.close()
         sess = pfdr.Session(wl.kind, wl.dtype, V, E, itMax=itMax, **kw, **dist_kw)
         sess.profile(True, only=timed)
         sess.run(steps)
         torch.cuda.synchronize()
+    if converge:
         del kw
     names = (wl.dominant, "edge_sweep", "edge_sweep_b", "vertex_sweep", "vertex_sweep_b",
              "sx_edge_sweep", "sx_vertex_sweep", "sx_vertex_wide", "gemv_rows",
              "gemv_cols", "halo_pull", "halo_push", "seq_evolution")
     stats = {k: sess.kernel_stats(k) for k in names}
-    res = res_timed if converge else sess.result()
     finite = bool(np.all(np.isfinite(res[0])))
     dev_bytes = sess.device_bytes()
     reordered = bool(sess.query("reordered"))
@@ -457,7 +510,7 @@ def main():
     ms_step = el_max / max(done, 1) * 1e3
     # per kernel family: SURVEY.md 8(d)'s bytes of that sweep (tools/workloads.py
     # kernel_bytes) over its mean time per iteration (HIP events, timed region)
-    pmc, pmc_note = pmc_summary(wl, E)
+    pmc, pmc_note = pmc_summary(wl, E) if args.full else (None, None)
     kbytes = wl.kernel_bytes(V, E)
     kernels = {}
     for fam, alg_b in kbytes.items():
@@ -543,7 +596,8 @@ def main():
             "timed_launches": "every %d-th launch of %s%s" % (period, ", ".join(
                 k for k in timed if stats.get(k, (0,))[0]),
                 ", in a profiled pass of the same length after the unprofiled (graph-replayed) "
-                "timed steps" if post_events else ", inside the timed steps"),
+                "timed steps" if post_events else ", inside the timed steps") if args.full
+            else "none (the per-kernel event pass runs with --full)",
             "launches": stats[dom_name][0] if dom_name in stats else 0,
             "dominant_rule": "the kernel family with the longest mean time per iteration",
             "mean_ms": dom.get("mean_ms"),

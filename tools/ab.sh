@@ -21,7 +21,7 @@ for w in ${WL:-headline}; do
     for r in $(seq ${ROUNDS:-2}); do
         for al in ${ARMS:-prev:scratch/prev.so new:}; do
             arm=${al%%:*}; L=${al#*:}
-            PFDR_LIB_PATH=$L timeout -k 10 ${LIMIT:-300} python bench.py --no-cpu-baseline \
+            PFDR_LIB_PATH=$L timeout -k 10 ${LIMIT:-300} python bench.py --full --no-cpu-baseline \
                 --workload $w ${BENCH_EXTRA:-} > "$OUT/${arm}_${w}_$r.log" 2>&1 || exit $?
             python - "$OUT/${arm}_${w}_$r.log" $arm $w <<'EOF'
 import json, sys

@@ -5,7 +5,7 @@
 #   TAG=r3l WL=headline bash tools/counters.sh
 set -u
 cd "$GRAFT_REPO_ROOT"; OUT=gpurun_out/${TAG:-cnt}_${WL:-headline}; mkdir -p $OUT; export TMPDIR=/tmp
-B="python bench.py --no-cpu-baseline --workload ${WL:-headline} ${BENCH_EXTRA:-} --steps 5 --warmup 1"
+B="python bench.py --full --no-cpu-baseline --workload ${WL:-headline} ${BENCH_EXTRA:-} --steps 5 --warmup 1"
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_VMEM_RD \
     -d $OUT/sq -o run --output-format csv -- $B > $OUT/sq.log 2>&1 || exit $?
 echo "sq ok"

@@ -3,7 +3,7 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; OUT=gpurun_out/${TAG:-grampmc}; mkdir -p $OUT; export TMPDIR=/tmp
 for wl in ${WLS:-c3 c3_ata}; do
-  B="python bench.py --no-cpu-baseline --workload $wl --steps 2 --warmup 0"
+  B="python bench.py --full --no-cpu-baseline --workload $wl --steps 2 --warmup 0"
   p=0
   for grp in "FETCH_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE"; do
     p=$((p+1))

@@ -18,15 +18,15 @@ step() {  # name limit cmd...
 }
 for what in "${@:-bench}"; do
   case $what in
-    bench) step bench 600 python bench.py ;;
-    bench100) step bench100 600 python bench.py --steps 100 --warmup 20 --no-cpu-baseline ;;
-    conv) step headline_conv 600 python bench.py --workload headline_conv ;;
-    conv1r) step headline_conv_rccl1 600 python bench.py --workload headline_conv \
+    bench) step bench 600 python bench.py --full ;;
+    bench100) step bench100 600 python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline ;;
+    conv) step headline_conv 600 python bench.py --full --workload headline_conv ;;
+    conv1r) step headline_conv_rccl1 600 python bench.py --full --workload headline_conv \
               --no-cpu-baseline --dist-selftest ;;
     wl) for w in ${WL:-c1 c2 c3 c3_ata c4 c5 headline_shuffled headline_slab8}; do
-            step "wl_$w" 600 python bench.py --workload "$w" ${BENCH_EXTRA:-}; done ;;
+            step "wl_$w" 600 python bench.py --full --workload "$w" ${BENCH_EXTRA:-}; done ;;
     prof) step rocprof_stats 600 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run \
-              --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
+              --output-format csv -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline ;;
     pmc) for w in ${PMC_WL:-headline}; do
             TAG=$T WL=$w bash tools/profile.sh > "$OUT/pmc_$w.log" 2>&1 || { tail -5 "$OUT/pmc_$w.log"; exit 1; }
             tail -3 "$OUT/pmc_$w.log"; done ;;

@@ -3,7 +3,7 @@
 #   TAG=r1o WL=headline E=60000000 V=10000000 bash tools/profile.sh
 set -u
 cd "$GRAFT_REPO_ROOT"; OUT=gpurun_out/${TAG:-prof}_${WL:-headline}; mkdir -p $OUT; export TMPDIR=/tmp
-B="python bench.py --no-cpu-baseline --workload ${WL:-headline} ${BENCH_EXTRA:-}"
+B="python bench.py --full --no-cpu-baseline --workload ${WL:-headline} ${BENCH_EXTRA:-}"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- $B --steps 20 --warmup 3 > $OUT/stats.log 2>&1 || exit $?
 echo "stats ok"
 timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o run --output-format csv -- $B --steps 5 --warmup 1 > $OUT/fetch.log 2>&1 || exit $?

@@ -6,7 +6,7 @@
 # only; plus a --stats pass for the kernel's duration.  Summary -> $OUT.
 set -u
 cd "$GRAFT_REPO_ROOT"; OUT=gpurun_out/${TAG:-mfma}; mkdir -p $OUT; export TMPDIR=/tmp
-B="python bench.py --no-cpu-baseline --workload ${WL:-c3} --steps 3 --warmup 1"
+B="python bench.py --full --no-cpu-baseline --workload ${WL:-c3} --steps 3 --warmup 1"
 KSEL="${KSEL:-k_gram_v}"  # substring of the kernel name (e.g. "k_gram_v<float, 0>" = A^tA)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- $B > $OUT/stats.log 2>&1 || exit $?
 echo "stats ok"

@@ -16,7 +16,7 @@ if [ -n "${TESTS:-}" ]; then
     tail -n 1 "$OUT/pytest.log"
 fi
 for w in ${WL:-}; do
-    timeout -k 10 ${LIMIT:-400} python bench.py --workload "$w" > "$OUT/$w.log" 2>&1 || exit $?
+    timeout -k 10 ${LIMIT:-400} python bench.py --full --workload "$w" > "$OUT/$w.log" 2>&1 || exit $?
     python - "$OUT/$w.log" "$w" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

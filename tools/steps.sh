@@ -10,7 +10,7 @@
 #   counters: tools/counters.sh of every WL for every ARM (SQ / TA / LDS counters)
 #   pmc    : rocprofv3 kernel stats + FETCH_SIZE / WRITE_SIZE passes of every WL (in-tree library,
 #            or PMC_LIB), summary gpurun_out/$TAG/pmc_<w>.json
-#   bench  : python bench.py $BENCH_ARGS
+#   bench  : python bench.py --full $BENCH_ARGS
 #   smoke  : __graft_entry__ build() + smoke()
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -41,7 +41,7 @@ for st in ${STEPS:-pytest}; do
                 for al in ${ARMS:-new:}; do
                     arm=${al%%:*}; L=${al#*:}; EV=""
                     case $L in *:*) EV=${L#*:}; L=${L%%:*} ;; esac  # name:lib:VAR=v,VAR=v
-                    env ${EV//,/ } PFDR_LIB_PATH=$L timeout -k 10 ${LIMIT:-300} python bench.py --no-cpu-baseline \
+                    env ${EV//,/ } PFDR_LIB_PATH=$L timeout -k 10 ${LIMIT:-300} python bench.py --full --no-cpu-baseline \
                         --workload $w ${BENCH_EXTRA:-} > "$OUT/${arm}_${w}_$r.log" 2>&1 || { rc=$?; break 3; }
                     line "$OUT/${arm}_${w}_$r.log" $arm $w
                 done
@@ -51,7 +51,7 @@ for st in ${STEPS:-pytest}; do
         rc=0
         for w in ${WL:-headline}; do
             P=$OUT/pmc_$w; mkdir -p $P
-            B="python bench.py --no-cpu-baseline --workload $w ${BENCH_EXTRA:-}"
+            B="python bench.py --full --no-cpu-baseline --workload $w ${BENCH_EXTRA:-}"
             PFDR_LIB_PATH=${PMC_LIB:-} timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $P/stats -o run \
                 --output-format csv -- $B --steps 20 --warmup 3 > $P/stats.log 2>&1 || { rc=$?; break; }
             PFDR_LIB_PATH=${PMC_LIB:-} timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE -d $P/fetch -o run \
@@ -80,7 +80,7 @@ EOF
             done
         done ;;
     bench)
-        timeout -k 10 ${LIMIT:-600} python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
+        timeout -k 10 ${LIMIT:-600} python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
         rc=$?; tail -n 1 "$OUT/bench.log" ;;
     smoke)
         timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1

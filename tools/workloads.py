@@ -11,7 +11,7 @@ Zv read and written, W_d1u, W_d1v, Th_d1), the vertex sweep the DR average's
 splitting weights (:491-497: Wu, Wv) and the per-vertex arrays; the
 simplex the same per (edge, label) (src/PFDR_graph_loss_d1_simplex.cpp:589-648).
 Only `headline` is the driver's bench line; the others are run with
-`python bench.py --workload cN` for DESIGN.md.
+`python bench.py --full --workload cN` for DESIGN.md.
 """
 import numpy as np
 

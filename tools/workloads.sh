@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for w in ${WL:-c1 c2 c3 c4 c5}; do
     t0=$(date +%s)
-    timeout -k 10 "${LIMIT:-400}" python bench.py --workload "$w" > "$OUT/$w.log" 2>&1
+    timeout -k 10 "${LIMIT:-400}" python bench.py --full --workload "$w" > "$OUT/$w.log" 2>&1
     rc=$?
     echo "[$w] rc=$rc $(( $(date +%s) - t0 ))s"
     tail -n 1 "$OUT/$w.log"
