@@ -16,8 +16,9 @@
 //   merge         deactivate edges between (relatively) equal components
 //                                                                  :863-886
 //
-// The maxflow itself (Boykov-Kolmogorov, sequential) stays with the caller
-// on the host: capacities go out, segments come back.
+// The cut itself is pfdr_cpgraph_mincut (pfdr_mincut.hip: push-relabel on
+// this graph, capacities and segments staying in HBM); a caller may still
+// take the capacities out and bring the segments of its own maxflow back.
 //
 // Graph state lives in HBM for the whole CP run: endpoints, TV / l1
 // weights, the incidence CSR (arc ids 2e + side ascending per vertex, i.e.
@@ -44,6 +45,7 @@
 #include <stdexcept>
 
 #include "pfdr_graph.hpp"
+#include "pfdr_mincut.hpp"
 #include "pfdr_monosum.hpp"
 
 namespace pfdr {
@@ -1142,6 +1144,10 @@ struct CpGraphBase {
     // the duplex driver's two-layer cut
     virtual void capacities_duplex(int positivity, void *tr, void *link, void *rc, int mem) = 0;
     int activate_duplex(const uint8_t *seg, int mem);
+    // the cut (pfdr_mincut.hip); mc_nbr: the head of every incidence position
+    DevBuf<int> mc_nbr;
+    MincutStats mc_stats;
+    virtual void mincut(int arcs, const void *tr, const void *rc, int mem, uint8_t *seg) = 0;
 };
 
 static hipMemcpyKind kind_in(int mem) {
@@ -1628,6 +1634,29 @@ struct CpGraph : CpGraphBase {
         PFDR_HIP(hipStreamSynchronize(s));
     }
 
+    void mincut(int arcs, const void *tr, const void *rc, int mem, uint8_t *seg) override {
+        DevBuf<real> btr, brc;
+        DevBuf<uint8_t> bseg;
+        const real *dtr = (const real *)tr, *drc = (const real *)rc;
+        uint8_t *dseg = seg;
+        HostPins hp(s);
+        if (mem != PFDR_MEM_DEVICE) {
+            btr.alloc(V);
+            bseg.alloc(V);
+            hp.copy(btr.p, tr, sizeof(real) * V, hipMemcpyHostToDevice);
+            if (E > 0) {
+                brc.alloc(E);
+                hp.copy(brc.p, rc, sizeof(real) * E, hipMemcpyHostToDevice);
+            }
+            dtr = btr.p;
+            drc = brc.p;
+            dseg = bseg.p;
+        }
+        pfdr::mincut<real>(V, E, inc, Eu.p, Ev.p, mc_nbr, arcs, dtr, drc, dseg, mc_stats, s);
+        if (mem != PFDR_MEM_DEVICE) hp.copy(seg, dseg, V, hipMemcpyDeviceToHost);
+        hp.release();
+    }
+
     int sx_merge(double eps) override {
         need_k("simplex_merge");
         if (!rP.p) throw std::runtime_error("simplex_merge: set the component values first");
@@ -1932,4 +1961,35 @@ extern "C" int pfdr_cpgraph_activate_duplex(pfdr_cpgraph *h, const uint8_t *segm
         const int n = h->g->activate_duplex(segment, mem);
         if (activated) *activated = n;
     })
+}
+
+// ------------------------------------------------------------ the cut --
+extern "C" int pfdr_cpgraph_mincut(pfdr_cpgraph *h, int arcs, const void *tr_cap,
+                                   const void *r_cap, int mem, uint8_t *segment, double *flow,
+                                   int64_t *rounds) {
+    const char *fn = "pfdr_cpgraph_mincut";
+    if (!h || !tr_cap || !segment || (h->g->E > 0 && !r_cap))
+        return report_error(fn, "null argument");
+    if (arcs != PFDR_ARCS_BOTH && arcs != PFDR_ARCS_FORWARD)
+        return report_error(fn, "arcs must be PFDR_ARCS_BOTH or PFDR_ARCS_FORWARD");
+    try {
+        pfdr::StreamScope sc_(h->g->s, h->g->dev);
+        h->g->mincut(arcs, tr_cap, r_cap, mem, segment);
+        if (flow) *flow = h->g->mc_stats.flow;
+        if (rounds) *rounds = h->g->mc_stats.rounds;
+    } catch (const pfdr::HipError &he) {
+        return report_error(fn, he);
+    } catch (const std::invalid_argument &ex) {
+        report_error(fn, ex.what());
+        return PFDR_ERR_ARG;
+    } catch (const std::exception &ex) {
+        return report_error(fn, ex.what());
+    }
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_cpgraph_mincut_relabels(pfdr_cpgraph *h, int64_t *relabels) {
+    if (!h || !relabels) return report_error("pfdr_cpgraph_mincut_relabels", "null argument");
+    *relabels = h->g->mc_stats.relabels;
+    return PFDR_OK;
 }

@@ -1,0 +1,450 @@
+// The whole cut pursuit, CP_PFDR_graph_quadratic_d1_l1<real> of the reference
+// (src/CP_PFDR_graph_quadratic_d1_l1.cpp), on one GPU: the loop of
+// INTEGRATION.md §7 over the library's own steps -- the graph steps of
+// pfdr_cpgraph.hip, the cut of pfdr_mincut.hip, the reduced problem of
+// pfdr_cp.hip and the PFDR solver -- with PFDR_MEM_DEVICE throughout.  Host
+// arrays come in once and Cv / rX go out once; in between only scalars and
+// N-sized vectors (the observations' side of a dense A) cross PCIe.
+//
+// The scalar sums (initialize :94-136, the iterate evolution :905-923 and the
+// objective :927-975) are added one by one in `real` in the reference's
+// order (ordered_segment_sums), like the reference built without OpenMP.
+#include <chrono>
+#include <cmath>
+#include <stdexcept>
+#include <vector>
+
+#include "pfdr_graph.hpp"
+
+namespace pfdr {
+
+namespace {
+
+struct AbiFail {  // a library call failed: its message is already recorded
+    int status;
+};
+#define CP_ABI(call)                               \
+    do {                                           \
+        const int st_ = (call);                    \
+        if (st_ != PFDR_OK) throw AbiFail{st_};    \
+    } while (0)
+
+// rA[n] = sum over the columns of A (N-by-V, column major), v ascending (:99-109)
+template <typename real>
+__global__ void k_cpq_colsum(int N, int V, const real *__restrict__ A, real *__restrict__ rA) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    real a = real(0);
+    for (long v = 0; v < V; v++) a += A[n + (long)N * v];
+    rA[n] = a;
+}
+
+// R = Y - rA rX, rv ascending (:889-901)
+template <typename real>
+__global__ void k_cpq_residual(int N, int rV, const real *__restrict__ rA,
+                               const real *__restrict__ rX, const real *__restrict__ Y,
+                               real *__restrict__ R) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    real a = real(0);
+    for (long rv = 0; rv < rV; rv++) a += rA[n + (long)N * rv] * rX[rv];
+    R[n] = Y[n] - a;
+}
+
+// terms of the iterate evolution (:911-918); the last partition becomes this one
+template <typename real>
+__global__ void k_cpq_evolution(int V, const int *__restrict__ Cv, const real *__restrict__ rX,
+                                int *__restrict__ Cv_, const real *__restrict__ rX_,
+                                real *__restrict__ td, real *__restrict__ tc) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const int rv = Cv[v];
+    const real a = rX[rv];
+    const real b = rX_[Cv_[v]] - a;
+    td[v] = b * b;
+    tc[v] = a * a;
+    Cv_[v] = rv;
+}
+
+// terms of 1/2 <X, AtA X> - <X, AtY> (:936-951): rows of a full rAA, or its diagonal
+template <typename real>
+__global__ void k_cpq_obj_quad(int rV, int full, const real *__restrict__ rAA,
+                               const real *__restrict__ rY, const real *__restrict__ rX,
+                               real *__restrict__ t) {
+    const int ru = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ru >= rV) return;
+    const real x = rX[ru];
+    if (full) {
+        const real *row = rAA + (long)rV * ru;
+        real b = real(0);
+        for (int rv = 0; rv < rV; rv++) b += row[rv] * rX[rv];
+        t[ru] = x * (real(0.5) * b - rY[ru]);
+    } else {
+        t[ru] = x * (real(0.5) * rAA[ru] * x - rY[ru]);
+    }
+}
+
+template <typename real>
+__global__ void k_cpq_obj_d1(int rE, const int *__restrict__ rEu, const int *__restrict__ rEv,
+                             const real *__restrict__ rLa, const real *__restrict__ rX,
+                             real *__restrict__ t) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= rE) return;
+    real b = rX[rEu[e]] - rX[rEv[e]];
+    if (b < real(0)) b = -b;
+    t[e] = rLa[e] * b;
+}
+
+template <typename real>
+__global__ void k_cpq_obj_l1(int rV, const real *__restrict__ rL1, const real *__restrict__ rX,
+                             real *__restrict__ t) {
+    const int rv = blockIdx.x * blockDim.x + threadIdx.x;
+    if (rv >= rV) return;
+    real b = rX[rv];
+    if (b < real(0)) b = -b;
+    t[rv] = rL1[rv] * b;
+}
+
+template <typename real>
+struct Driver {
+    hipStream_t s = lib_stream();
+    DevBuf<int> off{2};
+    DevBuf<real> one{1};
+
+    // ((0 + x[0]) + x[1]) + ... in real
+    real seq_sum(const real *x, long n) {
+        if (n <= 0) return real(0);
+        if (n >= (1L << 31)) throw std::runtime_error("sum of 2^31 or more terms");
+        const int h[2] = {0, (int)n};
+        PFDR_HIP(hipMemcpyAsync(off.p, h, sizeof h, hipMemcpyHostToDevice, s));
+        ordered_segment_sums<real>(1, off.p, nullptr, x, one.p, s);
+        real r;
+        PFDR_HIP(hipMemcpyAsync(&r, one.p, sizeof(real), hipMemcpyDeviceToHost, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+        return r;
+    }
+
+    template <typename T>
+    void up(DevBuf<T> &d, const T *h, size_t n, HostPins &hp) {
+        d.alloc(n ? n : 1);
+        if (n) hp.copy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+
+    void run(int V, int E, int N, int *rV_out, int *Cv, real *rX_out, const real *Y,
+             const real *A, const int *Eu, const int *Ev, const real *La_d1, const real *La_l1,
+             int positivity, real CP_difTol, int CP_itMax, int *CP_it_out, real rho,
+             real condMin, real difRcd, real difTol, int itMax, double *Time, real *Obj,
+             real *Dif, int verbose) {
+        using clock = std::chrono::steady_clock;
+        const auto t0 = clock::now();
+        const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
+        const real eps = (real(0) < CP_difTol && CP_difTol < Lim<real>::eps) ? CP_difTol
+                                                                            : Lim<real>::eps;
+        const int gV = grid_for(V);
+        // ---- the problem, once, into HBM
+        DevBuf<real> dY, dA, dLa, dL1;
+        DevBuf<int> dEu, dEv;
+        {
+            HostPins hp(s);
+            const size_t asz = N > 0 ? (size_t)N * V : N < 0 ? (size_t)V * V : A ? (size_t)V : 0;
+            up(dY, Y, N > 0 ? (size_t)N : (size_t)V, hp);
+            up(dA, A, asz, hp);
+            up(dEu, Eu, (size_t)E, hp);
+            up(dEv, Ev, (size_t)E, hp);
+            up(dLa, La_d1, (size_t)E, hp);
+            if (La_l1) up(dL1, La_l1, (size_t)V, hp);
+            hp.release();
+        }
+        const real *pA = A ? dA.p : nullptr;
+        pfdr_cpgraph *g = nullptr;
+        CP_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, La_l1 ? dL1.p : nullptr,
+                                   PFDR_MEM_DEVICE));
+        struct Hold {
+            pfdr_cpgraph *g;
+            ~Hold() { pfdr_cpgraph_destroy(g); }
+        } hold{g};
+
+        // ---- initialize (:94-175): the one-component solution
+        std::vector<real> hR, hY;  // N > 0: residual and observations (N-sized)
+        DevBuf<real> dR;
+        real rY = real(0), rAA = real(0), rL1s = real(0);
+        if (N > 0) {
+            DevBuf<real> drA(N);
+            k_cpq_colsum<real><<<grid_for(N), kBlock, 0, s>>>(N, V, dA.p, drA.p);
+            PFDR_HIP(hipGetLastError());
+            hR.resize(N);
+            hY.assign(Y, Y + N);
+            PFDR_HIP(hipMemcpyAsync(hR.data(), drA.p, sizeof(real) * N, hipMemcpyDeviceToHost, s));
+            PFDR_HIP(hipStreamSynchronize(s));
+            for (int n = 0; n < N; n++) {
+                rY += hR[n] * hY[n];
+                rAA += hR[n] * hR[n];
+            }
+        } else {
+            rY = seq_sum(dY.p, V);
+            if (N < 0) rAA = seq_sum(dA.p, (long)V * V);
+            else if (A) rAA = seq_sum(dA.p, V);
+            else rAA = (real)V;
+        }
+        if (La_l1) rL1s = seq_sum(dL1.p, V);
+        real x0 = real(0);
+        if (rY > rL1s) x0 = (rY - rL1s) / rAA;
+        else if (!positivity && rY < -rL1s) x0 = (rY + rL1s) / rAA;
+        int rV = 1, rE = 0;
+        DevBuf<real> drX(1);
+        PFDR_HIP(hipMemcpyAsync(drX.p, &x0, sizeof(real), hipMemcpyHostToDevice, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+        CP_ABI(pfdr_cpgraph_set_values(g, drX.p, PFDR_MEM_DEVICE));
+        if (N > 0) {
+            for (int n = 0; n < N; n++) hR[n] = hY[n] - hR[n] * x0;
+            dR.alloc(N);
+            PFDR_HIP(hipMemcpyAsync(dR.p, hR.data(), sizeof(real) * N, hipMemcpyHostToDevice, s));
+            PFDR_HIP(hipStreamSynchronize(s));
+        }
+        if (Obj) {
+            real a = real(0);
+            if (N > 0) {
+                for (int n = 0; n < N; n++) a += hR[n] * hR[n];
+                a *= real(0.5);
+            } else {
+                a = x0 * (real(0.5) * rAA * x0 - rY);
+            }
+            Obj[0] = a;
+            if (La_l1) Obj[0] += rL1s * (x0 < real(0) ? -x0 : x0);
+        }
+
+        // ---- cut pursuit
+        DevBuf<int> dCv(V), dVc(V), drVc((size_t)V + 1), dCv_;
+        DevBuf<real> drX_, dtr(V), drc(E > 0 ? E : 1), t1, t2;
+        DevBuf<uint8_t> dseg(V);
+        CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+        const bool track = CP_difTol > real(0) || Dif;
+        if (track) {
+            drX_.alloc(1);
+            dCv_.alloc(V);
+            t1.alloc(V);
+            t2.alloc(V);
+            PFDR_HIP(hipMemcpyAsync(drX_.p, drX.p, sizeof(real), hipMemcpyDeviceToDevice, s));
+            PFDR_HIP(hipMemcpyAsync(dCv_.p, dCv.p, sizeof(int) * V, hipMemcpyDeviceToDevice, s));
+            PFDR_HIP(hipStreamSynchronize(s));
+        }
+        const real difTol2 = CP_difTol * CP_difTol;
+        real dif = difTol2 > real(1) ? difTol2 : real(1);
+        int it = 0, pit = itMax;
+        auto cut = [&]() {
+            CP_ABI(pfdr_cpgraph_mincut(g, PFDR_ARCS_BOTH, dtr.p, drc.p, PFDR_MEM_DEVICE, dseg.p,
+                                       nullptr, nullptr));
+        };
+        for (;;) {
+            if (Time) Time[it] = std::chrono::duration<double>(clock::now() - t0).count();
+            if (verbose) {
+                printf("\n\tCut pursuit iteration %d (max. %d)\n", it, CP_itMax);
+                if (difTol2 > real(0)) printf("\trelative iterate evolution %g (tol. %g)\n",
+                                              (double)dif, (double)difTol2);
+                printf("\t%d connected component(s), %d reduced edge(s)\n", rV, rE);
+                fflush(stdout);
+            }
+            if (it == CP_itMax || dif < difTol2) break;
+            // steepest cuts (:337-556)
+            CP_ABI(pfdr_cpgraph_gradient(g, N, pA, dY.p, N > 0 ? dR.p : nullptr, PFDR_MEM_DEVICE,
+                                         nullptr));
+            int w = 0, n = 0;
+            if (!La_l1 && !positivity) {
+                CP_ABI(pfdr_cpgraph_capacities(g, 0, 0, dtr.p, drc.p, PFDR_MEM_DEVICE));
+                cut();
+                CP_ABI(pfdr_cpgraph_activate(g, dseg.p, PFDR_MEM_DEVICE, &w));
+            } else {
+                CP_ABI(pfdr_cpgraph_capacities(g, 1, positivity, dtr.p, drc.p, PFDR_MEM_DEVICE));
+                cut();
+                // the second cut's capacities, from the activity before the first's activations
+                CP_ABI(pfdr_cpgraph_capacities(g, 2, positivity, dtr.p, drc.p, PFDR_MEM_DEVICE));
+                CP_ABI(pfdr_cpgraph_activate(g, dseg.p, PFDR_MEM_DEVICE, &w));
+                cut();
+                CP_ABI(pfdr_cpgraph_activate(g, dseg.p, PFDR_MEM_DEVICE, &n));
+                w += n;
+            }
+            if (w == 0) {  // :556-563
+                if (track) {
+                    dif = real(0);
+                    if (Dif) Dif[it] = dif;
+                }
+                it++;
+                if (Obj) Obj[it] = Obj[it - 1];
+                continue;
+            }
+            // reduced graph and problem (:568-841)
+            CP_ABI(pfdr_cpgraph_components(g, &rV));
+            CP_ABI(pfdr_cpgraph_reduced_graph(g, (double)eps, &rE));
+            CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, dVc.p, drVc.p, PFDR_MEM_DEVICE));
+            DevBuf<int> rEu(rE > 0 ? rE : 1), rEv(rE > 0 ? rE : 1);
+            DevBuf<real> rLa(rE > 0 ? rE : 1), rL1;
+            if (La_l1) rL1.alloc(rV);
+            CP_ABI(pfdr_cpgraph_get_reduced(g, rEu.p, rEv.p, rLa.p, La_l1 ? rL1.p : nullptr,
+                                            PFDR_MEM_DEVICE));
+            const int preAt = N <= 0 || rV < (2L * N * pit) / ((long)N + pit);
+            DevBuf<real> rA, rAAd, rYd, L(rV);
+            if (N > 0) rA.alloc((size_t)N * rV);
+            if (preAt) {
+                rYd.alloc(rV);
+                rAAd.alloc(N == 0 ? (size_t)rV : (size_t)rV * rV);
+            }
+            if (sizeof(real) == 4)
+                CP_ABI(pfdr_cp_reduce_f32(N, V, (const float *)pA, (const float *)dY.p, rV, drVc.p,
+                                          dVc.p, preAt, PFDR_MEM_DEVICE, 1e-3f, 100, 10,
+                                          (float *)rA.p, (float *)rAAd.p, (float *)rYd.p,
+                                          (float *)L.p, nullptr));
+            else
+                CP_ABI(pfdr_cp_reduce_f64(N, V, (const double *)pA, (const double *)dY.p, rV,
+                                          drVc.p, dVc.p, preAt, PFDR_MEM_DEVICE, 1e-3, 100, 10,
+                                          (double *)rA.p, (double *)rAAd.p, (double *)rYd.p,
+                                          (double *)L.p, nullptr));
+            // PFDR from zero (:843-859)
+            drX.alloc(rV);
+            PFDR_HIP(hipMemsetAsync(drX.p, 0, sizeof(real) * rV, s));
+            PFDR_HIP(hipStreamSynchronize(s));
+            {
+                pfdr_problem p{};
+                p.kind = PFDR_KIND_L1;
+                p.dtype = dt;
+                p.mem = PFDR_MEM_DEVICE;
+                p.V = rV;
+                p.E = rE;
+                p.N = preAt ? (N == 0 ? 0 : -rV) : N;
+                p.X = drX.p;
+                p.Y = preAt ? rYd.p : dY.p;
+                p.A = preAt ? rAAd.p : rA.p;
+                p.Eu = rEu.p;
+                p.Ev = rEv.p;
+                p.La_d1 = rLa.p;
+                p.La_l1 = La_l1 ? rL1.p : nullptr;
+                p.positivity = positivity;
+                p.Ltype = PFDR_LIPSCHITZ_DIAG;
+                p.L = L.p;
+                p.rho = rho;
+                p.condMin = condMin;
+                p.difRcd = difRcd;
+                p.difTol = difTol;
+                p.itMax = itMax;
+                p.verbose = verbose;
+                pfdr_session *ses = nullptr;
+                CP_ABI(pfdr_session_create(&ses, &p));
+                struct SHold {
+                    pfdr_session *q;
+                    ~SHold() { pfdr_session_destroy(q); }
+                } sh{ses};
+                CP_ABI(pfdr_session_run(ses, itMax, &pit));
+                CP_ABI(pfdr_session_sync(ses));
+                const void *x = pfdr_session_device_x(ses);
+                if (!x) throw AbiFail{PFDR_ERR_STATE};
+                PFDR_HIP(hipMemcpyAsync(drX.p, x, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
+                PFDR_HIP(hipStreamSynchronize(s));
+            }
+            CP_ABI(pfdr_cpgraph_set_values(g, drX.p, PFDR_MEM_DEVICE));
+            CP_ABI(pfdr_cpgraph_merge(g, (double)eps, (double)CP_difTol, &n));
+            // progress (:888-923)
+            if (N > 0) {
+                k_cpq_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rV, rA.p, drX.p, dY.p, dR.p);
+                PFDR_HIP(hipGetLastError());
+            }
+            if (track) {
+                k_cpq_evolution<real><<<gV, kBlock, 0, s>>>(V, dCv.p, drX.p, dCv_.p, drX_.p, t1.p,
+                                                           t2.p);
+                PFDR_HIP(hipGetLastError());
+                dif = seq_sum(t1.p, V);
+                const real c = seq_sum(t2.p, V);
+                dif = c > eps ? dif / c : dif / eps;
+                drX_.alloc(rV);
+                PFDR_HIP(hipMemcpyAsync(drX_.p, drX.p, sizeof(real) * rV, hipMemcpyDeviceToDevice,
+                                        s));
+                PFDR_HIP(hipStreamSynchronize(s));
+                if (Dif) Dif[it] = dif;
+            }
+            it++;
+            if (Obj) {  // :927-975
+                real a = real(0);
+                DevBuf<real> t((size_t)std::max(rV, std::max(rE, 1)));
+                if (N > 0) {
+                    PFDR_HIP(hipMemcpyAsync(hR.data(), dR.p, sizeof(real) * N,
+                                            hipMemcpyDeviceToHost, s));
+                    PFDR_HIP(hipStreamSynchronize(s));
+                    for (int i = 0; i < N; i++) a += hR[i] * hR[i];
+                    a *= real(0.5);
+                } else {
+                    k_cpq_obj_quad<real><<<grid_for(rV), kBlock, 0, s>>>(rV, N < 0, rAAd.p, rYd.p,
+                                                                        drX.p, t.p);
+                    PFDR_HIP(hipGetLastError());
+                    a = seq_sum(t.p, rV);
+                }
+                Obj[it] = a;
+                if (rE > 0) {
+                    k_cpq_obj_d1<real><<<grid_for(rE), kBlock, 0, s>>>(rE, rEu.p, rEv.p, rLa.p,
+                                                                      drX.p, t.p);
+                    PFDR_HIP(hipGetLastError());
+                    Obj[it] += seq_sum(t.p, rE);
+                }
+                if (La_l1) {
+                    k_cpq_obj_l1<real><<<grid_for(rV), kBlock, 0, s>>>(rV, rL1.p, drX.p, t.p);
+                    PFDR_HIP(hipGetLastError());
+                    Obj[it] += seq_sum(t.p, rV);
+                }
+            }
+            PFDR_HIP(hipStreamSynchronize(s));  // the iteration's buffers leave scope
+        }
+        // ---- the result
+        *rV_out = rV;
+        if (CP_it_out) *CP_it_out = it;
+        HostPins hp(s);
+        hp.copy(Cv, dCv.p, sizeof(int) * V, hipMemcpyDeviceToHost);
+        hp.copy(rX_out, drX.p, sizeof(real) * rV, hipMemcpyDeviceToHost);
+        hp.release();
+    }
+};
+
+template <typename real>
+int cp_entry(const char *fn, int V, int E, int N, int *rV, int *Cv, real *rX, const real *Y,
+             const real *A, const int *Eu, const int *Ev, const real *La_d1, const real *La_l1,
+             int positivity, real CP_difTol, int CP_itMax, int *CP_it, real rho, real condMin,
+             real difRcd, real difTol, int itMax, double *Time, real *Obj, real *Dif,
+             int verbose) {
+    if (V <= 0 || E < 0 || !rV || !Cv || !rX || !Y || CP_itMax < 0 ||
+        (E > 0 && (!Eu || !Ev || !La_d1)))
+        return report_error(fn, "invalid arguments");
+    if (N != 0 && !A) return report_error(fn, "N != 0 needs A");
+    if (N < 0 && -N != V) return report_error(fn, "N < 0 needs A = A^tA and N = -V");
+    try {
+        Driver<real> d;
+        d.run(V, E, N, rV, Cv, rX, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax,
+              CP_it, rho, condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
+    } catch (const AbiFail &f) {
+        return f.status;
+    } catch (const HipError &h) {
+        return report_error(fn, h);
+    } catch (const std::exception &ex) {
+        return report_error(fn, ex.what());
+    }
+    return PFDR_OK;
+}
+
+}  // namespace
+
+}  // namespace pfdr
+
+extern "C" int pfdr_cp_quadratic_d1_l1_f32(int V, int E, int N, int *rV, int *Cv, float *rX,
+    const float *Y, const float *A, const int *Eu, const int *Ev, const float *La_d1,
+    const float *La_l1, int positivity, float CP_difTol, int CP_itMax, int *CP_it, float rho,
+    float condMin, float difRcd, float difTol, int itMax, double *Time, float *Obj, float *Dif,
+    int verbose) {
+    return pfdr::cp_entry<float>("pfdr_cp_quadratic_d1_l1_f32", V, E, N, rV, Cv, rX, Y, A, Eu, Ev,
+                                 La_d1, La_l1, positivity, CP_difTol, CP_itMax, CP_it, rho,
+                                 condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
+}
+
+extern "C" int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv, double *rX,
+    const double *Y, const double *A, const int *Eu, const int *Ev, const double *La_d1,
+    const double *La_l1, int positivity, double CP_difTol, int CP_itMax, int *CP_it, double rho,
+    double condMin, double difRcd, double difTol, int itMax, double *Time, double *Obj,
+    double *Dif, int verbose) {
+    return pfdr::cp_entry<double>("pfdr_cp_quadratic_d1_l1_f64", V, E, N, rV, Cv, rX, Y, A, Eu,
+                                  Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, CP_it, rho,
+                                  condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
+}

@@ -32,6 +32,8 @@ EVOLUTION_AUTO, EVOLUTION_SEQUENTIAL, EVOLUTION_TREE = 0, 1, 2
 # speculative decisions (PFDR_SPEC_*): own stream / split communicator,
 # serial on the session stream over one communicator, or none
 SPEC_AUTO, SPEC_SERIAL, SPEC_OFF = 0, 1, 2
+# which arcs of an edge r_cap[E] gives pfdr_cpgraph_mincut (PFDR_ARCS_*)
+ARCS_BOTH, ARCS_FORWARD = 0, 1
 ABI_VERSION = 4  # pfdr_abi_version() of the matching library
 
 # every C entry point of include/pfdr_mi355x.h
@@ -55,6 +57,8 @@ EXPORTED = (
     "pfdr_cpgraph_simplex_capacities", "pfdr_cpgraph_simplex_expand",
     "pfdr_cpgraph_simplex_activate", "pfdr_cpgraph_simplex_merge", "pfdr_cpgraph_simplex_labels",
     "pfdr_cpgraph_capacities_duplex", "pfdr_cpgraph_activate_duplex",
+    "pfdr_cpgraph_mincut", "pfdr_cpgraph_mincut_relabels",
+    "pfdr_cp_quadratic_d1_l1_f32", "pfdr_cp_quadratic_d1_l1_f64",
     "pfdr_session_create", "pfdr_session_run", "pfdr_session_prepare", "pfdr_session_result",
     "pfdr_session_device_x", "pfdr_session_set_profiling", "pfdr_session_profile_filter",
     "pfdr_session_kernel_stats", "pfdr_session_sync",
@@ -202,6 +206,32 @@ class Lib:
                   C.byref(it), _ptr(Obj, ct), _ptr(Dif, ct),
                   C.c_int(verbose)), "pfdr_quadratic_d1_l1_" + sfx)
         return X, it.value, Obj, Dif
+
+    def cp_quadratic_d1_l1(self, V, N, Y, A, Eu, Ev, La_d1, La_l1=None, positivity=0,
+                           CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
+                           difTol=1e-4, itMax=10000, verbose=0):
+        """pfdr_cp_quadratic_d1_l1: the whole cut pursuit -> (Cv[V] int32,
+        rX[rV], CP_it, Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1])"""
+        Y = np.ascontiguousarray(Y)
+        ct, sfx, _ = _real(Y.dtype)
+        dt = Y.dtype
+        A, La_d1, La_l1 = (_arr(a, dt) for a in (A, La_d1, La_l1))
+        Eu, Ev = _arr(Eu, np.int32), _arr(Ev, np.int32)
+        V = int(V)
+        Cv = np.zeros(V, np.int32)
+        rX = np.zeros(V, dt)
+        Obj = np.zeros(CP_itMax + 1, dt)
+        Dif = np.zeros(max(CP_itMax, 1), dt)
+        Time = np.zeros(CP_itMax + 1, np.float64)
+        rV, it = C.c_int(0), C.c_int(0)
+        fn = getattr(self.lib, "pfdr_cp_quadratic_d1_l1_" + sfx)
+        _check(fn(C.c_int(V), C.c_int(Eu.size), C.c_int(N), C.byref(rV), _ptr(Cv, C.c_int),
+                  _ptr(rX, ct), _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int), _ptr(Ev, C.c_int),
+                  _ptr(La_d1, ct), _ptr(La_l1, ct), C.c_int(int(positivity)), ct(CP_difTol),
+                  C.c_int(CP_itMax), C.byref(it), ct(rho), ct(condMin), ct(difRcd), ct(difTol),
+                  C.c_int(itMax), _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct),
+                  C.c_int(verbose)), "pfdr_cp_quadratic_d1_l1_" + sfx)
+        return Cv, rX[:rV.value].copy(), it.value, Obj, Dif[:CP_itMax], Time
 
     def quadratic_d1_bounds(self, X0, Y, A, N, Eu, Ev, La_d1, lo=-np.inf,
                             hi=np.inf, Ltype=SCAL, L=None, rho=1.5,
@@ -384,25 +414,10 @@ def PFDR_graph_loss_d1_simplex(Q, al, Eu, Ev, La_d1, rho, condMin, difRcd,
     return P.reshape(Q.shape, order="F"), it, Obj, Dif
 
 
-def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0,
-                      PFDR_rho=1.0, PFDR_condMin=1e-3, PFDR_difRcd=0.0, PFDR_difTol=1e-4,
-                      PFDR_itMax=10000, verbose=0):
-    """PFDR front-end with the conventions of the reference's Python binding
-    (python/CP_quadratic_l1_py.cpp:7-56, 130-258, which wraps CP; this
-    entry solves the same functional F(x) = 1/2 ||A x - obs||^2 + sum_e
-    edge_weight |x_u - x_v| + sum_v l1_weight |x_v| directly with PFDR):
-      * A scalar -> identity (its value discarded); A of shape (N,) ->
-        diagonal, obs and A pre-multiplied (obs*A, A*A) as the binding does
-        (:121-132); A of shape (N, V) -> the design matrix;
-      * edge_weight / l1_weight: array, or scalar broadcast to every edge /
-        vertex (the binding's broadcast loops run to V for both, :134-145,
-        an out-of-range write for the edge weights when E > V; here each
-        fills its own length);
-      * source / target: any integer dtype (the binding reinterprets uint32
-        as int32, :228-258);
-      * defaults from :64-72 (PFDR_rho 1, condMin 1e-3, difRcd 0, difTol
-        1e-4, itMax 1e4).
-    Returns (x, iterations)."""
+def _binding_inputs(obs, source, target, edge_weight, A, l1_weight):
+    """the input conventions of the reference's Python binding (see
+    PFDR_quadratic_l1) -> (dtype, N, V, mode, A, obs, Eu, Ev, edge weights[E],
+    l1 weights[V])"""
     obs = np.asarray(obs)
     if obs.dtype not in (np.float32, np.float64):
         raise TypeError("Type unknown, must be float32, float64, f4, or f8.")
@@ -427,6 +442,30 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
     ew = np.full(E, ew[0], dt) if ew.size == 1 else ew
     lw = np.asarray(l1_weight, dt).ravel()
     lw = np.full(V, lw[0], dt) if lw.size == 1 else lw
+    return dt, N, V, mode, A, obs, Eu, Ev, ew, lw
+
+
+def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0,
+                      PFDR_rho=1.0, PFDR_condMin=1e-3, PFDR_difRcd=0.0, PFDR_difTol=1e-4,
+                      PFDR_itMax=10000, verbose=0):
+    """PFDR front-end with the conventions of the reference's Python binding
+    (python/CP_quadratic_l1_py.cpp:7-56, 130-258, which wraps CP; this
+    entry solves the same functional F(x) = 1/2 ||A x - obs||^2 + sum_e
+    edge_weight |x_u - x_v| + sum_v l1_weight |x_v| directly with PFDR):
+      * A scalar -> identity (its value discarded); A of shape (N,) ->
+        diagonal, obs and A pre-multiplied (obs*A, A*A) as the binding does
+        (:121-132); A of shape (N, V) -> the design matrix;
+      * edge_weight / l1_weight: array, or scalar broadcast to every edge /
+        vertex (the binding's broadcast loops run to V for both, :134-145,
+        an out-of-range write for the edge weights when E > V; here each
+        fills its own length);
+      * source / target: any integer dtype (the binding reinterprets uint32
+        as int32, :228-258);
+      * defaults from :64-72 (PFDR_rho 1, condMin 1e-3, difRcd 0, difTol
+        1e-4, itMax 1e4).
+    Returns (x, iterations)."""
+    dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
+                                                             A, l1_weight)
     lib = Lib()
     X0 = np.zeros(V, dt)
     if mode == "identity":
@@ -446,6 +485,32 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
                                           positivity, SCAL, L, PFDR_rho, PFDR_condMin,
                                           PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose=verbose)
     return X, it
+
+
+def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0,
+                    PFDR_rho=1.0, PFDR_condMin=1e-3, CP_difTol=1e-3, PFDR_difRcd=0.0,
+                    PFDR_difTol=1e-4, CP_itMax=10, PFDR_itMax=10000, verbose=0):
+    """The reference's Python binding (python/CP_quadratic_l1_py.cpp:68-76,
+    188-259): cut pursuit for F(x) = 1/2 ||A x - obs||^2 + sum_e edge_weight
+    |x_u - x_v| + sum_v l1_weight |x_v|, same signature, defaults and input
+    conventions (those of PFDR_quadratic_l1), the whole loop on the GPU
+    (pfdr_cp_quadratic_d1_l1).  Returns (Cv, rX): the component of every
+    vertex (uint32, as the binding) and the value of every component."""
+    dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
+                                                             A, l1_weight)
+    lib = Lib()
+    kw = dict(positivity=positivity, CP_difTol=CP_difTol, CP_itMax=CP_itMax, rho=PFDR_rho,
+              condMin=PFDR_condMin, difRcd=PFDR_difRcd, difTol=PFDR_difTol, itMax=PFDR_itMax,
+              verbose=verbose)
+    if mode == "identity":
+        r = lib.cp_quadratic_d1_l1(V, 0, obs, None, Eu, Ev, ew, lw, **kw)
+    elif mode == "diagonal":
+        r = lib.cp_quadratic_d1_l1(V, 0, (obs * A).astype(dt), (A * A).astype(dt), Eu, Ev, ew,
+                                   lw, **kw)
+    else:
+        r = lib.cp_quadratic_d1_l1(V, N, obs, np.asfortranarray(A).ravel(order="F"), Eu, Ev, ew,
+                                   lw, **kw)
+    return r[0].astype(np.uint32), r[1]
 
 
 def proj_simplex_metric(X, M, A):
@@ -758,8 +823,8 @@ class CPGraph:
     """Device-resident cut-pursuit graph (pfdr_cpgraph_*, SURVEY.md §8(f)
     ranks 2-3): the full-graph steps of every CP iteration of
     src/CP_PFDR_graph_quadratic_d1_l1.cpp with the reference's results and
-    orders.  Arrays in and out are numpy (host); the maxflow between
-    ``capacities`` and ``activate`` is the caller's."""
+    orders.  Arrays in and out are numpy (host); the cut between
+    ``capacities`` and ``activate`` is ``mincut`` (or the caller's own)."""
 
     def __init__(self, V, Eu, Ev, La_d1, La_l1=None):
         La_d1 = np.asarray(La_d1)
@@ -871,6 +936,29 @@ class CPGraph:
         seg = np.ascontiguousarray(segment, np.uint8)
         n = C.c_int()
         self._call("pfdr_cpgraph_activate", self._p(seg), PFDR_MEM_HOST, C.byref(n))
+        return n.value
+
+    def mincut(self, tr_cap, r_cap, arcs=ARCS_BOTH):
+        """minimum cut of the capacities ``capacities`` / ``capacities_bounds``
+        (ARCS_BOTH) or ``simplex_capacities`` (ARCS_FORWARD) give -> (segment[V]
+        uint8: 0 = reachable from the source in the residual graph, the
+        reference's maxflow labels; cut value; push/relabel rounds)"""
+        tr = np.ascontiguousarray(tr_cap, self.dtype)
+        rc = np.ascontiguousarray(r_cap, self.dtype)
+        if tr.size != self.V or rc.size != self.E:
+            raise ValueError("mincut: tr_cap must have V and r_cap E entries")
+        seg = np.empty(self.V, np.uint8)
+        flow = C.c_double()
+        rounds = C.c_int64()
+        self._call("pfdr_cpgraph_mincut", C.c_int(int(arcs)), self._p(tr),
+                   self._p(rc) if self.E else None, PFDR_MEM_HOST, self._p(seg),
+                   C.byref(flow), C.byref(rounds))
+        return seg, flow.value, rounds.value
+
+    def mincut_relabels(self):
+        """global relabels of the last ``mincut``"""
+        n = C.c_int64()
+        self._call("pfdr_cpgraph_mincut_relabels", C.byref(n))
         return n.value
 
     # ---- the duplex driver's two-layer cut (src/CP_PFDR_graph_quadratic_d1_l1_duplex.cpp)

@@ -331,8 +331,9 @@ int pfdr_cp_reduce_f64(int N, int V, const double *A, const double *Y, int rV, c
 /* ------------------------------------------- cut-pursuit graph steps -- */
 /* The full-graph work of every cut-pursuit iteration around the reduced
  * PFDR solve, on a device-resident graph
- * (reference src/CP_PFDR_graph_quadratic_d1_l1.cpp; the maxflow stays with
- * the caller: capacities out, segments 0 = SOURCE / 1 = SINK back).  The
+ * (reference src/CP_PFDR_graph_quadratic_d1_l1.cpp; the cut is
+ * pfdr_cpgraph_mincut below, or the caller's own maxflow: capacities out,
+ * segments 0 = SOURCE / 1 = SINK back).  The
  * graph holds the endpoints, TV weights La_d1[E], l1 weights La_l1[V] (or
  * NULL), the activity of every edge (CP's is_active, initially none), the
  * components (Cv[V], Vc[V], rVc[rV + 1], initially one) and the component
@@ -385,6 +386,25 @@ int pfdr_cpgraph_capacities_bounds(pfdr_cpgraph *g, int cut, double min, double 
 int pfdr_cpgraph_activate(pfdr_cpgraph *g, const uint8_t *segment, int mem,
     int *activated);
 
+/* The cut of capacities tr_cap[V] (> 0 source, < 0 sink, may be infinite)
+ * and r_cap[E] (finite, >= 0) as the capacities entries above and the
+ * simplex driver's produce them, real type the graph's, host or device per
+ * mem.  segment[V] (in mem): 0 = SOURCE exactly for the vertices reachable
+ * from the source in the residual graph of a maximum flow, the set the
+ * reference's Boykov-Kolmogorov maxflow returns; 1 = SINK.  Synchronous
+ * push-relabel on the device, no floating atomics: the same inputs give the
+ * same bytes on every run.  flow (may be NULL): the value of the cut, summed
+ * in f64; rounds (may be NULL): push/relabel rounds run.  Uses the endpoints
+ * and the incidence lists only: activity, components and values are neither
+ * read nor changed.  NaN in tr_cap, negative, NaN or infinite r_cap:
+ * PFDR_ERR_ARG. */
+#define PFDR_ARCS_BOTH 0      /* r_cap[e] is the capacity of both arcs of edge e (l1, bounds drivers) */
+#define PFDR_ARCS_FORWARD 1   /* r_cap[e] is arc Eu[e] -> Ev[e]; the reverse arc has none (simplex driver) */
+int pfdr_cpgraph_mincut(pfdr_cpgraph *g, int arcs, const void *tr_cap, const void *r_cap,
+                        int mem, uint8_t *segment, double *flow, int64_t *rounds);
+/* global relabels (breadth-first labellings) of the last cut on g */
+int pfdr_cpgraph_mincut_relabels(pfdr_cpgraph *g, int64_t *relabels);
+
 /* The duplex driver, CP_PFDR_graph_quadratic_d1_l1_duplex, in its
  * non-differentiable case (graph created with La_l1; positivity optional):
  * one cut per iteration on a two-layer maxflow graph, node v (v1) and node
@@ -405,7 +425,7 @@ int pfdr_cpgraph_activate_duplex(pfdr_cpgraph *g, const uint8_t *segment, int me
  * without La_l1): K >= 2 labels, Q[V*K] and the component label vectors
  * rP[rV*K] vertex-major like the reference (P[v*K + k]); al = 0 linear,
  * 1 quadratic, (0, 1) smoothed-KL loss.  One CP iteration: gradient ->
- * for n = 1 .. K-1 { capacities(n) -> caller's maxflow -> expand(n,
+ * for n = 1 .. K-1 { capacities(n) -> mincut (PFDR_ARCS_FORWARD) -> expand(n,
  * segments) } -> activate -> pfdr_cpgraph_components -> reduced_graph ->
  * observations (the reduced problem's rQ, rLa_f and warm start rP) ->
  * PFDR_graph_loss_d1_simplex -> set_values -> merge.  eps: the driver's
@@ -437,6 +457,27 @@ int pfdr_cpgraph_simplex_activate(pfdr_cpgraph *g, int *activated);
 int pfdr_cpgraph_simplex_merge(pfdr_cpgraph *g, double eps, int *deactivated);
 /* Djv[V]: every vertex's alternative after the expansions so far */
 int pfdr_cpgraph_simplex_labels(pfdr_cpgraph *g, int *Djv, int mem);
+
+/* -------------------------------------------------- whole cut pursuit -- */
+/* CP_PFDR_graph_quadratic_d1_l1<real> of the reference (arguments as
+ * include/CP_PFDR_graph_quadratic_d1_l1.hpp:52-61, without the restart
+ * record), the loop above with pfdr_cpgraph_mincut and the PFDR solver,
+ * everything resident on the current device: host arrays come in once, Cv[V]
+ * and rX[*rV] (capacity V) go out once.  N > 0: A N-by-V column major, Y[N];
+ * N = -V: A = A^tA, Y = A^tY; N = 0: A diagonal or NULL, Y = A^tY.  La_l1
+ * may be NULL.  Time[CP_itMax + 1] (seconds), Obj[CP_itMax + 1],
+ * Dif[CP_itMax] and CP_it may be NULL.  The iterate evolution and the
+ * stopping rule (dif < CP_difTol^2) are the reference's. */
+int pfdr_cp_quadratic_d1_l1_f32(int V, int E, int N, int *rV, int *Cv, float *rX,
+    const float *Y, const float *A, const int *Eu, const int *Ev, const float *La_d1,
+    const float *La_l1, int positivity, float CP_difTol, int CP_itMax, int *CP_it,
+    float rho, float condMin, float difRcd, float difTol, int itMax,
+    double *Time, float *Obj, float *Dif, int verbose);
+int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv, double *rX,
+    const double *Y, const double *A, const int *Eu, const int *Ev, const double *La_d1,
+    const double *La_l1, int positivity, double CP_difTol, int CP_itMax, int *CP_it,
+    double rho, double condMin, double difRcd, double difTol, int itMax,
+    double *Time, double *Obj, double *Dif, int verbose);
 
 /* ------------------------------------------------------ multi-GPU comm -- */
 /* Partitioned sessions (quadratic solvers, identity or diagonal A): every
