@@ -59,6 +59,8 @@ EXPORTED = (
     "pfdr_cpgraph_capacities_duplex", "pfdr_cpgraph_activate_duplex",
     "pfdr_cpgraph_mincut", "pfdr_cpgraph_mincut_relabels",
     "pfdr_cp_quadratic_d1_l1_f32", "pfdr_cp_quadratic_d1_l1_f64",
+    "pfdr_cp_loss_d1_simplex_f32", "pfdr_cp_loss_d1_simplex_f64",
+    "pfdr_cp_loss_d1_simplex_stats",
     "pfdr_session_create", "pfdr_session_run", "pfdr_session_prepare", "pfdr_session_result",
     "pfdr_session_device_x", "pfdr_session_set_profiling", "pfdr_session_profile_filter",
     "pfdr_session_kernel_stats", "pfdr_session_sync",
@@ -68,6 +70,7 @@ EXPORTED = (
     "pfdr_loopback_destroy", "pfdr_plan_create", "pfdr_plan_get",
     "pfdr_plan_set_incoming", "pfdr_plan_finish", "pfdr_plan_destroy",
     "pfdr_set_devices", "pfdr_debug_tile_erec", "pfdr_debug_erec_layout",
+    "pfdr_debug_device_log",
     "pfdr_gen_knn_jitter_grid", "pfdr_gen_grid_edges",
     "pfdr_gen_piecewise_f32", "pfdr_gen_piecewise_f64",
     "pfdr_gen_uniform_f32", "pfdr_gen_uniform_f64", "pfdr_gen_matvec_f32",
@@ -232,6 +235,51 @@ class Lib:
                   C.c_int(itMax), _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct),
                   C.c_int(verbose)), "pfdr_cp_quadratic_d1_l1_" + sfx)
         return Cv, rX[:rV.value].copy(), it.value, Obj, Dif[:CP_itMax], Time
+
+    def cp_loss_d1_simplex(self, K, Q, Eu, Ev, La_d1, al=0.1, CP_difTol=1e-3, CP_itMax=10,
+                           rho=1.0, condMin=0.1, difRcd=0.0, difTol=1e-4, itMax=1000,
+                           verbose=0, time=True, obj=True, dif=True):
+        """pfdr_cp_loss_d1_simplex: the simplex driver's whole cut pursuit.  Q[V*K]
+        vertex-major (Q[v*K + k]) -> (Cv[V] int32, rP[rV*K] vertex-major, CP_it,
+        Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1]); a record not asked
+        for (obj / dif / time False) is passed as NULL and returned as None"""
+        Q = np.ascontiguousarray(Q).ravel()
+        ct, sfx, _ = _real(Q.dtype)
+        dt = Q.dtype
+        K, CP_itMax = int(K), int(CP_itMax)
+        V = Q.size // K
+        La_d1 = _arr(La_d1, dt)
+        Eu, Ev = _arr(Eu, np.int32), _arr(Ev, np.int32)
+        Cv = np.zeros(V, np.int32)
+        rP = np.zeros(V * K, dt)
+        Obj = np.zeros(CP_itMax + 1, dt) if obj else None
+        Dif = np.zeros(max(CP_itMax, 1), dt) if dif else None
+        Time = np.zeros(CP_itMax + 1, np.float64) if time else None
+        rV, it = C.c_int(0), C.c_int(0)
+        fn = getattr(self.lib, "pfdr_cp_loss_d1_simplex_" + sfx)
+        _check(fn(C.c_int(K), C.c_int(V), C.c_int(Eu.size), ct(al), C.byref(rV),
+                  _ptr(Cv, C.c_int), _ptr(rP, ct), _ptr(Q, ct), _ptr(Eu, C.c_int),
+                  _ptr(Ev, C.c_int), _ptr(La_d1, ct), ct(CP_difTol), C.c_int(CP_itMax),
+                  C.byref(it), ct(rho), ct(condMin), ct(difRcd), ct(difTol), C.c_int(itMax),
+                  _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct), C.c_int(verbose)),
+               "pfdr_cp_loss_d1_simplex_" + sfx)
+        return (Cv, rP[:rV.value * K].copy(), it.value, Obj,
+                None if Dif is None else Dif[:CP_itMax], Time)
+
+    def cp_loss_d1_simplex_stats(self, n_exp=64):
+        """pfdr_cp_loss_d1_simplex_stats of this thread's last cp_loss_d1_simplex
+        -> dict: seconds per phase, counts, rounds / relabels per expansion"""
+        sec = np.zeros(6, np.float64)
+        cnt = np.zeros(4, np.int64)
+        er, el = np.zeros(n_exp, np.int64), np.zeros(n_exp, np.int64)
+        _check(self.lib.pfdr_cp_loss_d1_simplex_stats(
+            _ptr(sec, C.c_double), _ptr(cnt, C.c_int64), _ptr(er, C.c_int64),
+            _ptr(el, C.c_int64), C.c_int(n_exp)), "pfdr_cp_loss_d1_simplex_stats")
+        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
+        out.update(zip(("expansions", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
+        out["exp_rounds"] = er[er >= 0]
+        out["exp_relabels"] = el[el >= 0]
+        return out
 
     def quadratic_d1_bounds(self, X0, Y, A, N, Eu, Ev, La_d1, lo=-np.inf,
                             hi=np.inf, Ltype=SCAL, L=None, rho=1.5,
@@ -412,6 +460,28 @@ def PFDR_graph_loss_d1_simplex(Q, al, Eu, Ev, La_d1, rho, condMin, difRcd,
         p0, q, K, Eu, Ev, np.asarray(La_d1, dt), al, La_f, rho, condMin,
         difRcd, difTol, itMax, obj, dif, verbose)
     return P.reshape(Q.shape, order="F"), it, Obj, Dif
+
+
+def CP_PFDR_graph_loss_d1_simplex(Q, al, Eu, Ev, La_d1, CP_difTol, CP_itMax, PFDR_rho,
+                                  PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose=0,
+                                  time=False, obj=False, dif=False):
+    """octave/mex/CP_PFDR_graph_loss_d1_simplex_mex.cpp: cut pursuit for the
+    loss (al = 0 linear, 1 quadratic, else smoothed Kullback-Leibler) of the
+    K-by-V Q (column v = Q[:, v]) plus sum_e La_d1 ||p_u - p_v||_1 over the
+    simplex, the whole loop on the GPU (pfdr_cp_loss_d1_simplex).  The dtype
+    follows Q (float32 or float64).  Returns (Cv, rP, CP_it, Time, Obj, Dif):
+    the component of every vertex (int32[V]), the K-by-rV label vectors of
+    the components -- the minimiser is rP[:, Cv] -- and the records asked for
+    (Time[CP_itMax + 1], Obj[CP_itMax + 1], Dif[CP_itMax]; None otherwise)."""
+    Q = np.asarray(Q)
+    dt = np.result_type(Q, np.float32)
+    K = Q.shape[0]
+    q = np.asfortranarray(Q, dt).ravel(order="F")
+    Eu, Ev = _edges(Eu, Ev)
+    Cv, rP, it, Obj, Dif, Time = Lib().cp_loss_d1_simplex(
+        K, q, Eu, Ev, np.asarray(La_d1, dt), al, CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
+        PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+    return Cv, rP.reshape((K, rP.size // K), order="F"), it, Time, Obj, Dif
 
 
 def _binding_inputs(obs, source, target, edge_weight, A, l1_weight):

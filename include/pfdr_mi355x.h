@@ -479,6 +479,48 @@ int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv, double *r
     double rho, double condMin, double difRcd, double difTol, int itMax,
     double *Time, double *Obj, double *Dif, int verbose);
 
+/* CP_PFDR_graph_loss_d1_simplex<real> of the reference (arguments as
+ * include/CP_PFDR_graph_loss_d1_simplex.hpp:41-48, without the restart
+ * record): the simplex driver's loop above -- gradient, K - 1 alpha-expansions
+ * with pfdr_cpgraph_mincut (PFDR_ARCS_FORWARD), activation, components,
+ * reduced graph, observations, the simplex PFDR solver from the components'
+ * own optima, merge -- everything resident on the current device: host arrays
+ * come in once, Cv[V] and rP go out once, and in between only scalars cross
+ * to the host.  Q[V*K] and rP vertex-major like the reference (Q[v*K + k],
+ * rP[rv*K + k]); rP is the caller's, capacity K*V, and receives K * (*rV)
+ * values.  al = 0 linear, 1 quadratic, (0, 1) smoothed-KL loss.
+ * Time[CP_itMax + 1] (seconds), Obj[CP_itMax + 1], Dif[CP_itMax] and CP_it may
+ * be NULL.  The iterate evolution (mean l1 change of the label vectors for
+ * CP_difTol < 1, the count of vertices whose first-largest label changed for
+ * CP_difTol >= 1), the stopping rule (dif < CP_difTol) and the driver's eps
+ * (:214-231 as compiled) are the reference's, every sum in its order.
+ * Two departures: Obj[0] is the functional at the one-component solution, by
+ * the formulas of every later Obj[k] (the reference's initialize() :119-146
+ * does not evaluate the functional for al != 0; for al = 0 the values agree);
+ * al < 0 or al > 1 is PFDR_ERR_ARG (the reference then reads constants it
+ * never set).  K < 2, V <= 0, E < 0, CP_itMax < 0 or a missing required
+ * pointer: PFDR_ERR_ARG before any device work.  E = 0 and V = 1 are valid. */
+int pfdr_cp_loss_d1_simplex_f32(int K, int V, int E, float al, int *rV, int *Cv, float *rP,
+    const float *Q, const int *Eu, const int *Ev, const float *La_d1,
+    float CP_difTol, int CP_itMax, int *CP_it,
+    float rho, float condMin, float difRcd, float difTol, int itMax,
+    double *Time, float *Obj, float *Dif, int verbose);
+int pfdr_cp_loss_d1_simplex_f64(int K, int V, int E, double al, int *rV, int *Cv, double *rP,
+    const double *Q, const int *Eu, const int *Ev, const double *La_d1,
+    double CP_difTol, int CP_itMax, int *CP_it,
+    double rho, double condMin, double difRcd, double difTol, int itMax,
+    double *Time, double *Obj, double *Dif, int verbose);
+/* Where the calling thread's last pfdr_cp_loss_d1_simplex_* call spent its
+ * time (host clock around synchronous steps; any output may be NULL):
+ * seconds[6] = gradient, the K - 1 cuts (capacities, cut, expansion), the
+ * other graph steps, PFDR, the evolution / objective sums, the whole call;
+ * counts[4] = expansions, push/relabel rounds and global relabels over all of
+ * them, PFDR iterations over all reduced problems; exp_rounds / exp_relabels
+ * [n_exp]: the same per expansion in call order, for the first 64 (-1 past
+ * the last one run or kept). */
+int pfdr_cp_loss_d1_simplex_stats(double *seconds, int64_t *counts, int64_t *exp_rounds,
+    int64_t *exp_relabels, int n_exp);
+
 /* ------------------------------------------------------ multi-GPU comm -- */
 /* Partitioned sessions (quadratic solvers, identity or diagonal A): every
  * rank passes its owned vertices (V of them, global ids [vtx_begin,
@@ -555,6 +597,10 @@ void pfdr_plan_destroy(pfdr_plan *plan);
 int pfdr_debug_tile_erec(int64_t E, int dtype, const int *Eu, const int *Ev,
     int blk_begin, int blk_count, int *rec, int64_t rec_ints);
 int pfdr_debug_erec_layout(int *ints, int *runs, int *nostage);
+/* out[i] = log(x[i]) on the device, the function (and compile flags) the
+ * smoothed-KL objective of pfdr_cp_loss_d1_simplex_* uses; host arrays of n
+ * reals of dtype PFDR_F32 / PFDR_F64.  For the test that measures its error. */
+int pfdr_debug_device_log(int dtype, int64_t n, const void *x, void *out);
 
 /* -------------------------------------------------- synthetic inputs -- */
 /* Host-side deterministic generators (no device needed), identical laws to
