@@ -61,6 +61,8 @@ EXPORTED = (
     "pfdr_cp_quadratic_d1_l1_f32", "pfdr_cp_quadratic_d1_l1_f64",
     "pfdr_cp_loss_d1_simplex_f32", "pfdr_cp_loss_d1_simplex_f64",
     "pfdr_cp_loss_d1_simplex_stats",
+    "pfdr_cp_quadratic_d1_bounds_f32", "pfdr_cp_quadratic_d1_bounds_f64",
+    "pfdr_cp_quadratic_d1_bounds_stats",
     "pfdr_session_create", "pfdr_session_run", "pfdr_session_prepare", "pfdr_session_result",
     "pfdr_session_device_x", "pfdr_session_set_profiling", "pfdr_session_profile_filter",
     "pfdr_session_kernel_stats", "pfdr_session_sync",
@@ -235,6 +237,44 @@ class Lib:
                   C.c_int(itMax), _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct),
                   C.c_int(verbose)), "pfdr_cp_quadratic_d1_l1_" + sfx)
         return Cv, rX[:rV.value].copy(), it.value, Obj, Dif[:CP_itMax], Time
+
+    def cp_quadratic_d1_bounds(self, V, N, Y, A, Eu, Ev, La_d1, lo=-np.inf, hi=np.inf,
+                               CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
+                               difTol=1e-4, itMax=10000, verbose=0):
+        """pfdr_cp_quadratic_d1_bounds: the bounds driver's whole cut pursuit for
+        the box lo <= x <= hi (+-inf: no bound) -> (Cv[V] int32, rX[rV], CP_it,
+        Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1])"""
+        Y = np.ascontiguousarray(Y)
+        ct, sfx, _ = _real(Y.dtype)
+        dt = Y.dtype
+        A, La_d1 = (_arr(a, dt) for a in (A, La_d1))
+        Eu, Ev = _arr(Eu, np.int32), _arr(Ev, np.int32)
+        V, CP_itMax = int(V), int(CP_itMax)
+        Cv = np.zeros(V, np.int32)
+        rX = np.zeros(V, dt)
+        Obj = np.zeros(CP_itMax + 1, dt)
+        Dif = np.zeros(max(CP_itMax, 1), dt)
+        Time = np.zeros(CP_itMax + 1, np.float64)
+        rV, it = C.c_int(0), C.c_int(0)
+        fn = getattr(self.lib, "pfdr_cp_quadratic_d1_bounds_" + sfx)
+        _check(fn(C.c_int(V), C.c_int(Eu.size), C.c_int(N), C.byref(rV), _ptr(Cv, C.c_int),
+                  _ptr(rX, ct), _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int), _ptr(Ev, C.c_int),
+                  _ptr(La_d1, ct), ct(lo), ct(hi), ct(CP_difTol), C.c_int(CP_itMax),
+                  C.byref(it), ct(rho), ct(condMin), ct(difRcd), ct(difTol), C.c_int(itMax),
+                  _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct), C.c_int(verbose)),
+               "pfdr_cp_quadratic_d1_bounds_" + sfx)
+        return Cv, rX[:rV.value].copy(), it.value, Obj, Dif[:CP_itMax], Time
+
+    def cp_quadratic_d1_bounds_stats(self):
+        """pfdr_cp_quadratic_d1_bounds_stats of this thread's last
+        cp_quadratic_d1_bounds -> dict: seconds per phase and counts"""
+        sec = np.zeros(6, np.float64)
+        cnt = np.zeros(4, np.int64)
+        _check(self.lib.pfdr_cp_quadratic_d1_bounds_stats(
+            _ptr(sec, C.c_double), _ptr(cnt, C.c_int64)), "pfdr_cp_quadratic_d1_bounds_stats")
+        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
+        out.update(zip(("n_cuts", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
+        return out
 
     def cp_loss_d1_simplex(self, K, Q, Eu, Ev, La_d1, al=0.1, CP_difTol=1e-3, CP_itMax=10,
                            rho=1.0, condMin=0.1, difRcd=0.0, difTol=1e-4, itMax=1000,
@@ -482,6 +522,68 @@ def CP_PFDR_graph_loss_d1_simplex(Q, al, Eu, Ev, La_d1, CP_difTol, CP_itMax, PFD
         K, q, Eu, Ev, np.asarray(La_d1, dt), al, CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
         PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
     return Cv, rP.reshape((K, rP.size // K), order="F"), it, Time, Obj, Dif
+
+
+def _cp_bounds(V, N, Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, rho, condMin, difRcd, difTol,
+               itMax, verbose, time, obj, dif):
+    """the three bounds front-ends' common call -> (Cv, rX, CP_it, Time, Obj, Dif),
+    the records not asked for None"""
+    Eu, Ev = _edges(Eu, Ev)
+    Cv, rX, it, Obj, Dif, Time = Lib().cp_quadratic_d1_bounds(
+        V, N, Y, A, Eu, Ev, np.asarray(La_d1, Y.dtype), Bnd[0], Bnd[1], CP_difTol, CP_itMax, rho,
+        condMin, difRcd, difTol, itMax, verbose)
+    return Cv, rX, it, Time if time else None, Obj if obj else None, Dif if dif else None
+
+
+def CP_PFDR_graph_quadratic_d1_bounds(Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho,
+                                      PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
+                                      verbose=0, time=False, obj=False, dif=False):
+    """octave/mex/CP_PFDR_graph_quadratic_d1_bounds_mex.cpp: cut pursuit for
+    1/2 ||y - A x||^2 + sum_e La_d1 |x_u - x_v| over Bnd[0] <= x <= Bnd[1]
+    (+-inf: no bound), A N-by-V, the whole loop on the GPU
+    (pfdr_cp_quadratic_d1_bounds).  Returns (Cv, rX, CP_it, Time, Obj, Dif): the
+    component of every vertex (int32[V]), the value of every component -- the
+    minimiser is rX[Cv] -- and the records asked for (None otherwise)."""
+    A = np.asarray(A)
+    dt = np.result_type(Y, np.float32)
+    N, V = A.shape
+    return _cp_bounds(V, N, np.asarray(Y, dt).ravel(), np.asfortranarray(A, dt).ravel(order="F"),
+                      Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
+                      PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+
+
+def CP_PFDR_graph_quadratic_d1_bounds_AtA(AtY, AtA, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax,
+                                          PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
+                                          PFDR_itMax, verbose=0, time=False, obj=False,
+                                          dif=False):
+    """octave/mex/CP_PFDR_graph_quadratic_d1_bounds_AtA_mex.cpp: the same with
+    A^tA (V-by-V) and A^ty given, N = -V; Obj leaves the constant 1/2 ||y||^2 out."""
+    dt = np.result_type(AtY, np.float32)
+    V = np.asarray(AtY).size
+    return _cp_bounds(V, -V, np.asarray(AtY, dt).ravel(),
+                      np.asfortranarray(AtA, dt).ravel(order="F"), Eu, Ev, La_d1, Bnd, CP_difTol,
+                      CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
+                      verbose, time, obj, dif)
+
+
+def CP_PFDR_graph_l22_d1_bounds(Y, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho,
+                                PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose=0,
+                                time=False, obj=False, dif=False):
+    """octave/mex/CP_PFDR_graph_l22_d1_bounds_mex.cpp:62-90: Y <- La_l2*Y, N = 0,
+    A = La_l2 (diagonal; a scalar: none); Obj += 1/2 ||y||^2_La_l2."""
+    Y = np.asarray(Y).ravel()
+    dt = np.result_type(Y, np.float32)
+    V = Y.size
+    La_l2 = _scal_or_vec(La_l2, V, dt)
+    Yw = (La_l2 * Y).astype(dt) if La_l2 is not None else Y.astype(dt)
+    Cv, rX, it, Time, Obj, Dif = _cp_bounds(
+        V, 0, Yw, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
+        PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+    if Obj is not None:
+        y = Y.astype(dt)
+        w = La_l2 if La_l2 is not None else np.ones(V, dt)
+        Obj[: it + 1] += float(np.sum(w.astype(np.float64) * y * y)) / 2.0
+    return Cv, rX, it, Time, Obj, Dif
 
 
 def _binding_inputs(obs, source, target, edge_weight, A, l1_weight):

@@ -479,6 +479,39 @@ int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv, double *r
     double rho, double condMin, double difRcd, double difTol, int itMax,
     double *Time, double *Obj, double *Dif, int verbose);
 
+/* CP_PFDR_graph_quadratic_d1_bounds<real> of the reference (arguments as
+ * include/CP_PFDR_graph_quadratic_d1_bounds.hpp, without the restart record):
+ * the same loop for the box min <= x <= max (+-HUGE_VAL: no bound) -- the
+ * one-component least-squares value projected onto the box, one cut when
+ * there is no bound and two otherwise (pfdr_cpgraph_capacities_bounds,
+ * pfdr_cpgraph_mincut with PFDR_ARCS_BOTH), the reduced problem solved by the
+ * bounds PFDR from zero -- everything resident on the current device: host
+ * arrays come in once, Cv[V] and rX[*rV] (the caller's, capacity V) go out
+ * once, and in between only scalars cross to the host.  N, A, Y, Time, Obj,
+ * Dif and CP_it as pfdr_cp_quadratic_d1_l1; every scalar sum is added one by
+ * one in the reference's order.  One departure: min > max or a NaN bound is
+ * PFDR_ERR_ARG (the reference clamps to min and hands PFDR an empty box).
+ * V <= 0, E < 0, CP_itMax < 0, a missing required pointer, N != 0 without A or
+ * N < 0 with -N != V: PFDR_ERR_ARG before any device work.  min == max, E = 0
+ * and V = 1 are valid. */
+int pfdr_cp_quadratic_d1_bounds_f32(int V, int E, int N, int *rV, int *Cv, float *rX,
+    const float *Y, const float *A, const int *Eu, const int *Ev, const float *La_d1,
+    float min, float max, float CP_difTol, int CP_itMax, int *CP_it,
+    float rho, float condMin, float difRcd, float difTol, int itMax,
+    double *Time, float *Obj, float *Dif, int verbose);
+int pfdr_cp_quadratic_d1_bounds_f64(int V, int E, int N, int *rV, int *Cv, double *rX,
+    const double *Y, const double *A, const int *Eu, const int *Ev, const double *La_d1,
+    double min, double max, double CP_difTol, int CP_itMax, int *CP_it,
+    double rho, double condMin, double difRcd, double difTol, int itMax,
+    double *Time, double *Obj, double *Dif, int verbose);
+/* Where the calling thread's last pfdr_cp_quadratic_d1_bounds_* call spent
+ * its time (host clock around synchronous steps; either output may be NULL):
+ * seconds[6] = gradient, the cuts (capacities, cut, activation), the other
+ * graph steps and the reduction, PFDR, the evolution / objective sums, the
+ * whole call; counts[4] = cuts, push/relabel rounds and global relabels over
+ * all of them, PFDR iterations over all reduced problems. */
+int pfdr_cp_quadratic_d1_bounds_stats(double *seconds, int64_t *counts);
+
 /* CP_PFDR_graph_loss_d1_simplex<real> of the reference (arguments as
  * include/CP_PFDR_graph_loss_d1_simplex.hpp:41-48, without the restart
  * record): the simplex driver's loop above -- gradient, K - 1 alpha-expansions
