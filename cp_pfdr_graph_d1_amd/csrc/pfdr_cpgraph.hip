@@ -1148,6 +1148,10 @@ struct CpGraphBase {
     DevBuf<int> mc_nbr;
     MincutStats mc_stats;
     virtual void mincut(int arcs, const void *tr, const void *rc, int mem, uint8_t *seg) = 0;
+    // the two-layer cut and its 2V-node CSR (built by the first such cut)
+    DuplexNet mc_duplex;
+    virtual void mincut_duplex(const void *tr, const void *link, const void *rc, int mem,
+                               uint8_t *seg) = 0;
 };
 
 static hipMemcpyKind kind_in(int mem) {
@@ -1657,6 +1661,34 @@ struct CpGraph : CpGraphBase {
         hp.release();
     }
 
+    void mincut_duplex(const void *tr, const void *link, const void *rc, int mem,
+                       uint8_t *seg) override {
+        DevBuf<real> btr, bln, brc;
+        DevBuf<uint8_t> bseg;
+        const real *dtr = (const real *)tr, *dln = (const real *)link, *drc = (const real *)rc;
+        uint8_t *dseg = seg;
+        const size_t V2 = 2 * (size_t)V;
+        HostPins hp(s);
+        if (mem != PFDR_MEM_DEVICE) {
+            btr.alloc(V2);
+            bln.alloc(V);
+            bseg.alloc(V2);
+            hp.copy(btr.p, tr, sizeof(real) * V2, hipMemcpyHostToDevice);
+            hp.copy(bln.p, link, sizeof(real) * V, hipMemcpyHostToDevice);
+            if (E > 0) {
+                brc.alloc(E);
+                hp.copy(brc.p, rc, sizeof(real) * E, hipMemcpyHostToDevice);
+            }
+            dtr = btr.p;
+            dln = bln.p;
+            drc = brc.p;
+            dseg = bseg.p;
+        }
+        pfdr::mincut_duplex<real>(V, E, mc_duplex, Eu.p, Ev.p, dtr, dln, drc, dseg, mc_stats, s);
+        if (mem != PFDR_MEM_DEVICE) hp.copy(seg, dseg, V2, hipMemcpyDeviceToHost);
+        hp.release();
+    }
+
     int sx_merge(double eps) override {
         need_k("simplex_merge");
         if (!rP.p) throw std::runtime_error("simplex_merge: set the component values first");
@@ -1975,6 +2007,28 @@ extern "C" int pfdr_cpgraph_mincut(pfdr_cpgraph *h, int arcs, const void *tr_cap
     try {
         pfdr::StreamScope sc_(h->g->s, h->g->dev);
         h->g->mincut(arcs, tr_cap, r_cap, mem, segment);
+        if (flow) *flow = h->g->mc_stats.flow;
+        if (rounds) *rounds = h->g->mc_stats.rounds;
+    } catch (const pfdr::HipError &he) {
+        return report_error(fn, he);
+    } catch (const std::invalid_argument &ex) {
+        report_error(fn, ex.what());
+        return PFDR_ERR_ARG;
+    } catch (const std::exception &ex) {
+        return report_error(fn, ex.what());
+    }
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_cpgraph_mincut_duplex(pfdr_cpgraph *h, const void *tr_cap,
+                                          const void *r_link, const void *r_cap, int mem,
+                                          uint8_t *segment, double *flow, int64_t *rounds) {
+    const char *fn = "pfdr_cpgraph_mincut_duplex";
+    if (!h || !tr_cap || !r_link || !segment || (h->g->E > 0 && !r_cap))
+        return report_error(fn, "null argument");
+    try {
+        pfdr::StreamScope sc_(h->g->s, h->g->dev);
+        h->g->mincut_duplex(tr_cap, r_link, r_cap, mem, segment);
         if (flow) *flow = h->g->mc_stats.flow;
         if (rounds) *rounds = h->g->mc_stats.rounds;
     } catch (const pfdr::HipError &he) {

@@ -6,6 +6,10 @@
 // arrays come in once and Cv / rX go out once; in between only scalars and
 // N-sized vectors (the observations' side of a dense A) cross PCIe.
 //
+// The same loop with one two-layer cut per iteration is the duplex driver,
+// CP_PFDR_graph_quadratic_d1_l1_duplex<real> (pfdr_cp_quadratic_d1_l1_duplex_*):
+// its source differs from the l1 driver's in the graph and the cut only.
+//
 // The scalar sums (initialize :94-136, the iterate evolution :905-923 and the
 // objective :927-975) are added one by one in `real` in the reference's
 // order (ordered_segment_sums), like the reference built without OpenMP.
@@ -28,6 +32,14 @@ struct AbiFail {  // a library call failed: its message is already recorded
         const int st_ = (call);                    \
         if (st_ != PFDR_OK) throw AbiFail{st_};    \
     } while (0)
+
+// What a call spent where (pfdr_cp_quadratic_d1_l1_duplex_stats: the last
+// duplex call on this thread).
+struct Stats {
+    double gradient = 0, cuts = 0, graph = 0, pfdr = 0, sums = 0, total = 0;
+    int64_t ncuts = 0, rounds = 0, relabels = 0, pfdr_it = 0;
+};
+thread_local Stats g_duplex_stats;
 
 // rA[n] = sum over the columns of A (N-by-V, column major), v ascending (:99-109)
 template <typename real>
@@ -105,11 +117,21 @@ __global__ void k_cpq_obj_l1(int rV, const real *__restrict__ rL1, const real *_
     t[rv] = rL1[rv] * b;
 }
 
+// duplex: CP_PFDR_graph_quadratic_d1_l1_duplex (src/CP_PFDR_graph_quadratic_d1_l1_duplex.cpp),
+// which differs from the l1 driver in the graph and the cut only: one
+// two-layer cut per iteration when there is an l1 term or positivity
 template <typename real>
 struct Driver {
+    using clock = std::chrono::steady_clock;
     hipStream_t s = lib_stream();
+    bool duplex = false;
+    Stats st;  // of the last run
     DevBuf<int> off{2};
     DevBuf<real> one{1};
+
+    static double since(clock::time_point t) {
+        return std::chrono::duration<double>(clock::now() - t).count();
+    }
 
     // ((0 + x[0]) + x[1]) + ... in real
     real seq_sum(const real *x, long n) {
@@ -135,8 +157,10 @@ struct Driver {
              int positivity, real CP_difTol, int CP_itMax, int *CP_it_out, real rho,
              real condMin, real difRcd, real difTol, int itMax, double *Time, real *Obj,
              real *Dif, int verbose) {
-        using clock = std::chrono::steady_clock;
         const auto t0 = clock::now();
+        auto t = t0;
+        st = Stats{};
+        const bool two = duplex && (La_l1 || positivity);  // the two-layer cut
         const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
         const real eps = (real(0) < CP_difTol && CP_difTol < Lim<real>::eps) ? CP_difTol
                                                                             : Lim<real>::eps;
@@ -215,8 +239,10 @@ struct Driver {
 
         // ---- cut pursuit
         DevBuf<int> dCv(V), dVc(V), drVc((size_t)V + 1), dCv_;
-        DevBuf<real> drX_, dtr(V), drc(E > 0 ? E : 1), t1, t2;
-        DevBuf<uint8_t> dseg(V);
+        const size_t nodes = two ? 2 * (size_t)V : (size_t)V;  // of the cut's network
+        DevBuf<real> drX_, dtr(nodes), drc(E > 0 ? E : 1), dlink, t1, t2;
+        DevBuf<uint8_t> dseg(nodes);
+        if (two) dlink.alloc(V);
         CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
         const bool track = CP_difTol > real(0) || Dif;
         if (track) {
@@ -232,11 +258,20 @@ struct Driver {
         real dif = difTol2 > real(1) ? difTol2 : real(1);
         int it = 0, pit = itMax;
         auto cut = [&]() {
-            CP_ABI(pfdr_cpgraph_mincut(g, PFDR_ARCS_BOTH, dtr.p, drc.p, PFDR_MEM_DEVICE, dseg.p,
-                                       nullptr, nullptr));
+            int64_t rounds = 0, relabels = 0;
+            if (two)
+                CP_ABI(pfdr_cpgraph_mincut_duplex(g, dtr.p, dlink.p, drc.p, PFDR_MEM_DEVICE,
+                                                  dseg.p, nullptr, &rounds));
+            else
+                CP_ABI(pfdr_cpgraph_mincut(g, PFDR_ARCS_BOTH, dtr.p, drc.p, PFDR_MEM_DEVICE,
+                                           dseg.p, nullptr, &rounds));
+            CP_ABI(pfdr_cpgraph_mincut_relabels(g, &relabels));
+            st.ncuts++;
+            st.rounds += rounds;
+            st.relabels += relabels;
         };
         for (;;) {
-            if (Time) Time[it] = std::chrono::duration<double>(clock::now() - t0).count();
+            if (Time) Time[it] = since(t0);
             if (verbose) {
                 printf("\n\tCut pursuit iteration %d (max. %d)\n", it, CP_itMax);
                 if (difTol2 > real(0)) printf("\trelative iterate evolution %g (tol. %g)\n",
@@ -246,10 +281,18 @@ struct Driver {
             }
             if (it == CP_itMax || dif < difTol2) break;
             // steepest cuts (:337-556)
+            t = clock::now();
             CP_ABI(pfdr_cpgraph_gradient(g, N, pA, dY.p, N > 0 ? dR.p : nullptr, PFDR_MEM_DEVICE,
                                          nullptr));
+            st.gradient += since(t);
+            t = clock::now();
             int w = 0, n = 0;
-            if (!La_l1 && !positivity) {
+            if (two) {  // duplex :469-545
+                CP_ABI(pfdr_cpgraph_capacities_duplex(g, positivity, dtr.p, dlink.p, drc.p,
+                                                      PFDR_MEM_DEVICE));
+                cut();
+                CP_ABI(pfdr_cpgraph_activate_duplex(g, dseg.p, PFDR_MEM_DEVICE, &w));
+            } else if (!La_l1 && !positivity) {
                 CP_ABI(pfdr_cpgraph_capacities(g, 0, 0, dtr.p, drc.p, PFDR_MEM_DEVICE));
                 cut();
                 CP_ABI(pfdr_cpgraph_activate(g, dseg.p, PFDR_MEM_DEVICE, &w));
@@ -263,6 +306,7 @@ struct Driver {
                 CP_ABI(pfdr_cpgraph_activate(g, dseg.p, PFDR_MEM_DEVICE, &n));
                 w += n;
             }
+            st.cuts += since(t);
             if (w == 0) {  // :556-563
                 if (track) {
                     dif = real(0);
@@ -273,6 +317,7 @@ struct Driver {
                 continue;
             }
             // reduced graph and problem (:568-841)
+            t = clock::now();
             CP_ABI(pfdr_cpgraph_components(g, &rV));
             CP_ABI(pfdr_cpgraph_reduced_graph(g, (double)eps, &rE));
             CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, dVc.p, drVc.p, PFDR_MEM_DEVICE));
@@ -298,7 +343,9 @@ struct Driver {
                                           drVc.p, dVc.p, preAt, PFDR_MEM_DEVICE, 1e-3, 100, 10,
                                           (double *)rA.p, (double *)rAAd.p, (double *)rYd.p,
                                           (double *)L.p, nullptr));
+            st.graph += since(t);
             // PFDR from zero (:843-859)
+            t = clock::now();
             drX.alloc(rV);
             PFDR_HIP(hipMemsetAsync(drX.p, 0, sizeof(real) * rV, s));
             PFDR_HIP(hipStreamSynchronize(s));
@@ -339,8 +386,13 @@ struct Driver {
                 PFDR_HIP(hipMemcpyAsync(drX.p, x, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
                 PFDR_HIP(hipStreamSynchronize(s));
             }
+            st.pfdr += since(t);
+            st.pfdr_it += pit;
+            t = clock::now();
             CP_ABI(pfdr_cpgraph_set_values(g, drX.p, PFDR_MEM_DEVICE));
             CP_ABI(pfdr_cpgraph_merge(g, (double)eps, (double)CP_difTol, &n));
+            st.graph += since(t);
+            t = clock::now();
             // progress (:888-923)
             if (N > 0) {
                 k_cpq_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rV, rA.p, drX.p, dY.p, dR.p);
@@ -389,6 +441,7 @@ struct Driver {
                 }
             }
             PFDR_HIP(hipStreamSynchronize(s));  // the iteration's buffers leave scope
+            st.sums += since(t);
         }
         // ---- the result
         *rV_out = rV;
@@ -397,15 +450,16 @@ struct Driver {
         hp.copy(Cv, dCv.p, sizeof(int) * V, hipMemcpyDeviceToHost);
         hp.copy(rX_out, drX.p, sizeof(real) * rV, hipMemcpyDeviceToHost);
         hp.release();
+        st.total = since(t0);
     }
 };
 
 template <typename real>
-int cp_entry(const char *fn, int V, int E, int N, int *rV, int *Cv, real *rX, const real *Y,
-             const real *A, const int *Eu, const int *Ev, const real *La_d1, const real *La_l1,
-             int positivity, real CP_difTol, int CP_itMax, int *CP_it, real rho, real condMin,
-             real difRcd, real difTol, int itMax, double *Time, real *Obj, real *Dif,
-             int verbose) {
+int cp_entry(const char *fn, bool duplex, int V, int E, int N, int *rV, int *Cv, real *rX,
+             const real *Y, const real *A, const int *Eu, const int *Ev, const real *La_d1,
+             const real *La_l1, int positivity, real CP_difTol, int CP_itMax, int *CP_it, real rho,
+             real condMin, real difRcd, real difTol, int itMax, double *Time, real *Obj,
+             real *Dif, int verbose) {
     if (V <= 0 || E < 0 || !rV || !Cv || !rX || !Y || CP_itMax < 0 ||
         (E > 0 && (!Eu || !Ev || !La_d1)))
         return report_error(fn, "invalid arguments");
@@ -413,6 +467,13 @@ int cp_entry(const char *fn, int V, int E, int N, int *rV, int *Cv, real *rX, co
     if (N < 0 && -N != V) return report_error(fn, "N < 0 needs A = A^tA and N = -V");
     try {
         Driver<real> d;
+        d.duplex = duplex;
+        struct Keep {  // what the call spent, also when it fails half way
+            Driver<real> &d;
+            ~Keep() {
+                if (d.duplex) g_duplex_stats = d.st;
+            }
+        } keep{d};
         d.run(V, E, N, rV, Cv, rX, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax,
               CP_it, rho, condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
     } catch (const AbiFail &f) {
@@ -434,9 +495,9 @@ extern "C" int pfdr_cp_quadratic_d1_l1_f32(int V, int E, int N, int *rV, int *Cv
     const float *La_l1, int positivity, float CP_difTol, int CP_itMax, int *CP_it, float rho,
     float condMin, float difRcd, float difTol, int itMax, double *Time, float *Obj, float *Dif,
     int verbose) {
-    return pfdr::cp_entry<float>("pfdr_cp_quadratic_d1_l1_f32", V, E, N, rV, Cv, rX, Y, A, Eu, Ev,
-                                 La_d1, La_l1, positivity, CP_difTol, CP_itMax, CP_it, rho,
-                                 condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
+    return pfdr::cp_entry<float>("pfdr_cp_quadratic_d1_l1_f32", false, V, E, N, rV, Cv, rX, Y,
+                                 A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, CP_it,
+                                 rho, condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
 }
 
 extern "C" int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv, double *rX,
@@ -444,7 +505,44 @@ extern "C" int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv
     const double *La_l1, int positivity, double CP_difTol, int CP_itMax, int *CP_it, double rho,
     double condMin, double difRcd, double difTol, int itMax, double *Time, double *Obj,
     double *Dif, int verbose) {
-    return pfdr::cp_entry<double>("pfdr_cp_quadratic_d1_l1_f64", V, E, N, rV, Cv, rX, Y, A, Eu,
-                                  Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, CP_it, rho,
-                                  condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
+    return pfdr::cp_entry<double>("pfdr_cp_quadratic_d1_l1_f64", false, V, E, N, rV, Cv, rX, Y,
+                                  A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, CP_it,
+                                  rho, condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
+}
+
+extern "C" int pfdr_cp_quadratic_d1_l1_duplex_f32(int V, int E, int N, int *rV, int *Cv,
+    float *rX, const float *Y, const float *A, const int *Eu, const int *Ev, const float *La_d1,
+    const float *La_l1, int positivity, float CP_difTol, int CP_itMax, int *CP_it, float rho,
+    float condMin, float difRcd, float difTol, int itMax, double *Time, float *Obj, float *Dif,
+    int verbose) {
+    return pfdr::cp_entry<float>("pfdr_cp_quadratic_d1_l1_duplex_f32", true, V, E, N, rV, Cv, rX,
+                                 Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax,
+                                 CP_it, rho, condMin, difRcd, difTol, itMax, Time, Obj, Dif,
+                                 verbose);
+}
+
+extern "C" int pfdr_cp_quadratic_d1_l1_duplex_f64(int V, int E, int N, int *rV, int *Cv,
+    double *rX, const double *Y, const double *A, const int *Eu, const int *Ev,
+    const double *La_d1, const double *La_l1, int positivity, double CP_difTol, int CP_itMax,
+    int *CP_it, double rho, double condMin, double difRcd, double difTol, int itMax,
+    double *Time, double *Obj, double *Dif, int verbose) {
+    return pfdr::cp_entry<double>("pfdr_cp_quadratic_d1_l1_duplex_f64", true, V, E, N, rV, Cv,
+                                  rX, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
+                                  CP_itMax, CP_it, rho, condMin, difRcd, difTol, itMax, Time, Obj,
+                                  Dif, verbose);
+}
+
+extern "C" int pfdr_cp_quadratic_d1_l1_duplex_stats(double *seconds, int64_t *counts) {
+    const pfdr::Stats &st = pfdr::g_duplex_stats;
+    if (seconds) {
+        const double v[6] = {st.gradient, st.cuts, st.graph, st.pfdr, st.sums, st.total};
+        for (int i = 0; i < 6; i++) seconds[i] = v[i];
+    }
+    if (counts) {
+        counts[0] = st.ncuts;
+        counts[1] = st.rounds;
+        counts[2] = st.relabels;
+        counts[3] = st.pfdr_it;
+    }
+    return PFDR_OK;
 }

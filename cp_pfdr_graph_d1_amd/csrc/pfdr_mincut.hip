@@ -37,6 +37,10 @@
 // distances by a level-synchronous breadth-first search from the nodes with
 // negative excess; unreached nodes get height V and drop out for good.  The
 // last such search, run when no active node is left, is the answer.
+//
+// The duplex driver's two-layer cut (mincut_duplex) runs the same rounds over
+// a CSR of 2V nodes: only the residuals' initialisation and the cut's value
+// know the edge classes (layer edges with both arcs, one-way links).
 #include <climits>
 #include <stdexcept>
 
@@ -69,17 +73,43 @@ __global__ void k_mc_nbr(long n, const unsigned *__restrict__ idx, const int *__
     }
 }
 
-// ex = -tr_cap; residuals of the reversed network: both slots r_cap[e], or
-// (forward arcs Eu -> Ev only) slot 2e + 1 alone
-template <typename real>
-__global__ void k_mc_init(int V, long E, int both, const real *__restrict__ tr,
-                          const real *__restrict__ rc, real *__restrict__ ex,
-                          real *__restrict__ res, int *__restrict__ pushed, McCtl *ctl) {
-    int b = 0;
-    const long n = max((long)V, E);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+// the two-layer network's edge list: e and E + e (endpoints + V) for edge e,
+// 2E + v for the link (v, V + v)
+__global__ void k_mc_duplex_edges(int V, long E, const int *__restrict__ Eu,
+                                  const int *__restrict__ Ev, int *__restrict__ u,
+                                  int *__restrict__ v) {
+    const long m = max((long)V, E);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
          i += (long)gridDim.x * blockDim.x) {
+        if (i < E) {
+            const int a = Eu[i], b = Ev[i];
+            u[i] = a;
+            v[i] = b;
+            u[E + i] = V + a;
+            v[E + i] = V + b;
+        }
         if (i < V) {
+            u[2 * E + i] = (int)i;
+            v[2 * E + i] = V + (int)i;
+        }
+    }
+}
+
+// ex = -tr_cap; residuals of the reversed network: both slots r_cap[e], or
+// (forward arcs Eu -> Ev only) slot 2e + 1 alone.  n nodes, E edges with a
+// capacity.  Two layers (L > 0 link arcs, n = 2L): edge e has r_cap[e] on both
+// slots of edge ids e and E + e, link v (edge id 2E + v, arc v -> L + v) has
+// r_link[v] on its reversed-network slot only.
+template <typename real>
+__global__ void k_mc_init(int n, long E, int both, int L, const real *__restrict__ tr,
+                          const real *__restrict__ rc, const real *__restrict__ link,
+                          real *__restrict__ ex, real *__restrict__ res,
+                          int *__restrict__ pushed, McCtl *ctl) {
+    int b = 0;
+    const long m = max((long)n, E);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
+         i += (long)gridDim.x * blockDim.x) {
+        if (i < n) {
             const real t = tr[i];
             if (t != t) b = 1;
             ex[i] = -t;
@@ -92,6 +122,15 @@ __global__ void k_mc_init(int V, long E, int both, const real *__restrict__ tr,
             r.v[0] = both ? c : real(0);
             r.v[1] = c;
             *reinterpret_cast<Pk<real, 2> *>(res + 2 * i) = r;
+            if (L > 0) *reinterpret_cast<Pk<real, 2> *>(res + 2 * (E + i)) = r;
+        }
+        if (i < L) {
+            const real c = link[i];
+            if (!(c >= real(0) && c < Lim<real>::huge)) b = 1;
+            Pk<real, 2> r;
+            r.v[0] = real(0);
+            r.v[1] = c;
+            *reinterpret_cast<Pk<real, 2> *>(res + 2 * (2 * E + i)) = r;
         }
     }
     if (__syncthreads_or(b) && threadIdx.x == 0) atomicOr(&ctl->bad, 1);
@@ -241,31 +280,38 @@ __global__ void k_mc_segment(int V, const int *__restrict__ h, uint8_t *__restri
 
 // value of the cut (SOURCE = 0 -> SINK = 1 arcs of the original network) in
 // f64: per-thread sums over a fixed grid, a fixed tree per block, the block
-// sums stored and added in order
+// sums stored and added in order.  Two layers (L > 0, n = 2L): the n
+// terminals, every edge once per layer, then the links.
 template <typename real>
-__global__ __launch_bounds__(kBlock) void k_mc_cut(int V, long E, int both,
+__global__ __launch_bounds__(kBlock) void k_mc_cut(int n, long E, int both, int L,
                                                   const real *__restrict__ tr,
                                                   const real *__restrict__ rc,
+                                                  const real *__restrict__ link,
                                                   const int *__restrict__ Eu,
                                                   const int *__restrict__ Ev,
                                                   const uint8_t *__restrict__ seg,
                                                   double *__restrict__ part) {
     __shared__ double lds[kBlock / kWave];
     double c = 0;
-    const long n = (long)V + E;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+    const long m = (long)n + E + L;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < m;
          i += (long)gridDim.x * blockDim.x) {
-        if (i < V) {
+        if (i < n) {
             const real t = tr[i];
             if (seg[i]) {
                 if (t > real(0)) c += (double)t;
             } else if (t < real(0)) {
                 c -= (double)t;
             }
-        } else {
-            const long e = i - V;
-            const int su = seg[Eu[e]], sv = seg[Ev[e]];
+        } else if (i < n + E) {
+            const long e = i - n;
+            const int u = Eu[e], v = Ev[e];
+            const int su = seg[u], sv = seg[v];
             if (su != sv && (both || su == 0)) c += (double)rc[e];
+            if (L > 0 && seg[L + u] != seg[L + v]) c += (double)rc[e];
+        } else {
+            const long v = i - n - E;
+            if (seg[v] == 0 && seg[L + v] != 0) c += (double)link[v];
         }
     }
     c = block_sum(c, lds);
@@ -282,18 +328,16 @@ __global__ void k_mc_cut_sum(int n, const double *__restrict__ part, double *__r
 
 }  // namespace
 
+// The rounds over a CSR of n nodes and Et edges (2 Et slots).  One layer
+// (L = 0): n = V, Et = E.  Two layers: n = 2L, Et = 2E + L.
 template <typename real>
-void mincut(int V, long E, const Incidence &inc, const int *Eu, const int *Ev, DevBuf<int> &nbr,
-            int arcs, const real *tr, const real *rc, uint8_t *seg, MincutStats &st,
-            hipStream_t s) {
-    const int both = arcs == PFDR_ARCS_BOTH;
-    const long n2 = 2 * E;
+static void run_cut(int n, long E, int L, const Incidence &inc, const int *nbr, const int *Eu,
+                    const int *Ev, int both, const real *tr, const real *rc, const real *link,
+                    uint8_t *seg, MincutStats &st, hipStream_t s) {
+    const int V = n;  // the nodes of the network
+    const long Et = L > 0 ? 2 * E + L : E;
+    const long n2 = 2 * Et;
     const int gv = grid_for(V);
-    if (E > 0 && nbr.n != (size_t)n2) {
-        nbr.alloc(n2);
-        k_mc_nbr<<<std::min(grid_for(n2), 8192), kBlock, 0, s>>>(n2, inc.idx.p, Eu, Ev, nbr.p);
-        PFDR_HIP(hipGetLastError());
-    }
     DevBuf<real> ex(V), res(n2 > 0 ? n2 : 2), delta(n2 > 0 ? n2 : 2);
     DevBuf<int> hA(V), hB(V), pushed(V);
     DevBuf<McCtl> ctl(1);
@@ -307,22 +351,24 @@ void mincut(int V, long E, const Incidence &inc, const int *Eu, const int *Ev, D
 
     PFDR_HIP(hipMemsetAsync(ctl.p, 0, sizeof(McCtl), s));
     k_mc_init<real><<<std::min(grid_for(std::max((long)V, E)), 8192), kBlock, 0, s>>>(
-        V, E, both, tr, rc, ex.p, res.p, pushed.p, ctl.p);
+        V, E, both, L, tr, rc, link, ex.p, res.p, pushed.p, ctl.p);
     PFDR_HIP(hipGetLastError());
     poll();
     if (hc->bad)
         throw std::invalid_argument(
-            "mincut: tr_cap must not be NaN, r_cap must be finite and >= 0");
+            L > 0 ? "mincut_duplex: tr_cap must not be NaN, r_cap and r_link must be finite "
+                    "and >= 0"
+                  : "mincut: tr_cap must not be NaN, r_cap must be finite and >= 0");
 
     // exact heights into hA; returns the number of levels that labelled
     auto relabel = [&]() {
         k_mc_bfs_init<real><<<gv, kBlock, 0, s>>>(V, ex.p, hA.p, ctl.p);
         int depth = 0;
-        if (E > 0) {
+        if (Et > 0) {
             int l = 0;
             for (int batch = 16;; batch = 64) {
                 for (int i = 0; i < batch; i++, l++)
-                    k_mc_bfs_level<real><<<gv, kBlock, 0, s>>>(V, l, inc.ptr.p, inc.idx.p, nbr.p,
+                    k_mc_bfs_level<real><<<gv, kBlock, 0, s>>>(V, l, inc.ptr.p, inc.idx.p, nbr,
                                                                res.p, hA.p, ctl.p);
                 PFDR_HIP(hipGetLastError());
                 poll();
@@ -353,13 +399,13 @@ void mincut(int V, long E, const Incidence &inc, const int *Eu, const int *Ev, D
         // act = R0: round R0 + 1 runs
         PFDR_HIP(hipMemcpyAsync(&ctl.p->act, &R0, sizeof(int), hipMemcpyHostToDevice, s));
         for (int i = 0; i < P; i += 2) {
-            k_mc_push<real><<<gv, kBlock, 0, s>>>(V, R + 1, inc.ptr.p, inc.idx.p, nbr.p, ex.p,
+            k_mc_push<real><<<gv, kBlock, 0, s>>>(V, R + 1, inc.ptr.p, inc.idx.p, nbr, ex.p,
                                                   hA.p, res.p, delta.p, pushed.p, ctl.p);
-            k_mc_apply<real><<<gv, kBlock, 0, s>>>(V, R + 1, inc.ptr.p, inc.idx.p, nbr.p, ex.p,
+            k_mc_apply<real><<<gv, kBlock, 0, s>>>(V, R + 1, inc.ptr.p, inc.idx.p, nbr, ex.p,
                                                    hA.p, hB.p, res.p, delta.p, pushed.p, ctl.p);
-            k_mc_push<real><<<gv, kBlock, 0, s>>>(V, R + 2, inc.ptr.p, inc.idx.p, nbr.p, ex.p,
+            k_mc_push<real><<<gv, kBlock, 0, s>>>(V, R + 2, inc.ptr.p, inc.idx.p, nbr, ex.p,
                                                   hB.p, res.p, delta.p, pushed.p, ctl.p);
-            k_mc_apply<real><<<gv, kBlock, 0, s>>>(V, R + 2, inc.ptr.p, inc.idx.p, nbr.p, ex.p,
+            k_mc_apply<real><<<gv, kBlock, 0, s>>>(V, R + 2, inc.ptr.p, inc.idx.p, nbr, ex.p,
                                                    hB.p, hA.p, res.p, delta.p, pushed.p, ctl.p);
             R += 2;
         }
@@ -370,7 +416,7 @@ void mincut(int V, long E, const Incidence &inc, const int *Eu, const int *Ev, D
     }
 
     k_mc_segment<<<gv, kBlock, 0, s>>>(V, hA.p, seg);
-    k_mc_cut<real><<<kCutGrid, kBlock, 0, s>>>(V, E, both, tr, rc, Eu, Ev, seg, part.p);
+    k_mc_cut<real><<<kCutGrid, kBlock, 0, s>>>(V, E, both, L, tr, rc, link, Eu, Ev, seg, part.p);
     k_mc_cut_sum<<<1, kWave, 0, s>>>(kCutGrid, part.p, part.p + kCutGrid);
     PFDR_HIP(hipGetLastError());
     double *hf = reinterpret_cast<double *>(hc);
@@ -379,11 +425,57 @@ void mincut(int V, long E, const Incidence &inc, const int *Eu, const int *Ev, D
     st.flow = *hf;
 }
 
+template <typename real>
+void mincut(int V, long E, const Incidence &inc, const int *Eu, const int *Ev, DevBuf<int> &nbr,
+            int arcs, const real *tr, const real *rc, uint8_t *seg, MincutStats &st,
+            hipStream_t s) {
+    const long n2 = 2 * E;
+    if (E > 0 && nbr.n != (size_t)n2) {
+        nbr.alloc(n2);
+        k_mc_nbr<<<std::min(grid_for(n2), 8192), kBlock, 0, s>>>(n2, inc.idx.p, Eu, Ev, nbr.p);
+        PFDR_HIP(hipGetLastError());
+    }
+    run_cut<real>(V, E, 0, inc, nbr.p, Eu, Ev, arcs == PFDR_ARCS_BOTH, tr, rc, nullptr, seg, st,
+                  s);
+}
+
+void DuplexNet::build(int V, long E, const int *Eu, const int *Ev, hipStream_t s) {
+    const long Et = 2 * E + V;
+    if (2 * Et > (long)INT_MAX)
+        throw std::invalid_argument(
+            "mincut_duplex: 2 (2E + V) incidence slots do not fit the CSR's int offsets");
+    DevBuf<int> u(Et), v(Et);
+    k_mc_duplex_edges<<<std::min(grid_for(std::max((long)V, E)), 8192), kBlock, 0, s>>>(
+        V, E, Eu, Ev, u.p, v.p);
+    PFDR_HIP(hipGetLastError());
+    build_incidence(u.p, v.p, 2 * V, Et, inc, s);
+    nbr.alloc(2 * Et);
+    k_mc_nbr<<<std::min(grid_for(2 * Et), 8192), kBlock, 0, s>>>(2 * Et, inc.idx.p, u.p, v.p,
+                                                                 nbr.p);
+    PFDR_HIP(hipGetLastError());
+    PFDR_HIP(hipStreamSynchronize(s));  // u, v leave scope
+    built = true;
+}
+
+template <typename real>
+void mincut_duplex(int V, long E, DuplexNet &net, const int *Eu, const int *Ev, const real *tr,
+                   const real *link, const real *rc, uint8_t *seg, MincutStats &st,
+                   hipStream_t s) {
+    if (!net.built) net.build(V, E, Eu, Ev, s);
+    run_cut<real>(2 * V, E, V, net.inc, net.nbr.p, Eu, Ev, 1, tr, rc, link, seg, st, s);
+}
+
 template void mincut<float>(int, long, const Incidence &, const int *, const int *,
                             DevBuf<int> &, int, const float *, const float *, uint8_t *,
                             MincutStats &, hipStream_t);
 template void mincut<double>(int, long, const Incidence &, const int *, const int *,
                              DevBuf<int> &, int, const double *, const double *, uint8_t *,
                              MincutStats &, hipStream_t);
+template void mincut_duplex<float>(int, long, DuplexNet &, const int *, const int *,
+                                   const float *, const float *, const float *, uint8_t *,
+                                   MincutStats &, hipStream_t);
+template void mincut_duplex<double>(int, long, DuplexNet &, const int *, const int *,
+                                    const double *, const double *, const double *, uint8_t *,
+                                    MincutStats &, hipStream_t);
 
 }  // namespace pfdr

@@ -57,8 +57,10 @@ EXPORTED = (
     "pfdr_cpgraph_simplex_capacities", "pfdr_cpgraph_simplex_expand",
     "pfdr_cpgraph_simplex_activate", "pfdr_cpgraph_simplex_merge", "pfdr_cpgraph_simplex_labels",
     "pfdr_cpgraph_capacities_duplex", "pfdr_cpgraph_activate_duplex",
-    "pfdr_cpgraph_mincut", "pfdr_cpgraph_mincut_relabels",
+    "pfdr_cpgraph_mincut", "pfdr_cpgraph_mincut_relabels", "pfdr_cpgraph_mincut_duplex",
     "pfdr_cp_quadratic_d1_l1_f32", "pfdr_cp_quadratic_d1_l1_f64",
+    "pfdr_cp_quadratic_d1_l1_duplex_f32", "pfdr_cp_quadratic_d1_l1_duplex_f64",
+    "pfdr_cp_quadratic_d1_l1_duplex_stats",
     "pfdr_cp_loss_d1_simplex_f32", "pfdr_cp_loss_d1_simplex_f64",
     "pfdr_cp_loss_d1_simplex_stats",
     "pfdr_cp_quadratic_d1_bounds_f32", "pfdr_cp_quadratic_d1_bounds_f64",
@@ -214,7 +216,7 @@ class Lib:
 
     def cp_quadratic_d1_l1(self, V, N, Y, A, Eu, Ev, La_d1, La_l1=None, positivity=0,
                            CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
-                           difTol=1e-4, itMax=10000, verbose=0):
+                           difTol=1e-4, itMax=10000, verbose=0, _entry="pfdr_cp_quadratic_d1_l1_"):
         """pfdr_cp_quadratic_d1_l1: the whole cut pursuit -> (Cv[V] int32,
         rX[rV], CP_it, Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1])"""
         Y = np.ascontiguousarray(Y)
@@ -229,14 +231,35 @@ class Lib:
         Dif = np.zeros(max(CP_itMax, 1), dt)
         Time = np.zeros(CP_itMax + 1, np.float64)
         rV, it = C.c_int(0), C.c_int(0)
-        fn = getattr(self.lib, "pfdr_cp_quadratic_d1_l1_" + sfx)
+        fn = getattr(self.lib, _entry + sfx)
         _check(fn(C.c_int(V), C.c_int(Eu.size), C.c_int(N), C.byref(rV), _ptr(Cv, C.c_int),
                   _ptr(rX, ct), _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int), _ptr(Ev, C.c_int),
                   _ptr(La_d1, ct), _ptr(La_l1, ct), C.c_int(int(positivity)), ct(CP_difTol),
                   C.c_int(CP_itMax), C.byref(it), ct(rho), ct(condMin), ct(difRcd), ct(difTol),
                   C.c_int(itMax), _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct),
-                  C.c_int(verbose)), "pfdr_cp_quadratic_d1_l1_" + sfx)
+                  C.c_int(verbose)), _entry + sfx)
         return Cv, rX[:rV.value].copy(), it.value, Obj, Dif[:CP_itMax], Time
+
+    def cp_quadratic_d1_l1_duplex(self, V, N, Y, A, Eu, Ev, La_d1, La_l1=None, positivity=0,
+                                  CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3,
+                                  difRcd=0.0, difTol=1e-4, itMax=10000, verbose=0):
+        """pfdr_cp_quadratic_d1_l1_duplex: the duplex driver's whole cut pursuit
+        (one two-layer cut per iteration); arguments and returns as
+        cp_quadratic_d1_l1"""
+        return self.cp_quadratic_d1_l1(V, N, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
+                                       CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose,
+                                       _entry="pfdr_cp_quadratic_d1_l1_duplex_")
+
+    def cp_quadratic_d1_l1_duplex_stats(self):
+        """pfdr_cp_quadratic_d1_l1_duplex_stats of this thread's last
+        cp_quadratic_d1_l1_duplex -> dict: seconds per phase and counts"""
+        sec = np.zeros(6, np.float64)
+        cnt = np.zeros(4, np.int64)
+        _check(self.lib.pfdr_cp_quadratic_d1_l1_duplex_stats(
+            _ptr(sec, C.c_double), _ptr(cnt, C.c_int64)), "pfdr_cp_quadratic_d1_l1_duplex_stats")
+        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
+        out.update(zip(("n_cuts", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
+        return out
 
     def cp_quadratic_d1_bounds(self, V, N, Y, A, Eu, Ev, La_d1, lo=-np.inf, hi=np.inf,
                                CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
@@ -586,6 +609,57 @@ def CP_PFDR_graph_l22_d1_bounds(Y, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMa
     return Cv, rX, it, Time, Obj, Dif
 
 
+def _cp_duplex(V, N, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, rho, condMin,
+               difRcd, difTol, itMax, verbose, time, obj, dif):
+    """the duplex front-ends' common call -> (Cv, rX, CP_it, Time, Obj, Dif),
+    the records not asked for None"""
+    Eu, Ev = _edges(Eu, Ev)
+    dt = Y.dtype
+    Cv, rX, it, Obj, Dif, Time = Lib().cp_quadratic_d1_l1_duplex(
+        V, N, Y, A, Eu, Ev, np.asarray(La_d1, dt), _scal_or_vec(La_l1, V, dt), positivity,
+        CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose)
+    return Cv, rX, it, Time if time else None, Obj if obj else None, Dif if dif else None
+
+
+def CP_PFDR_graph_quadratic_d1_l1_duplex(Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
+                                         CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd,
+                                         PFDR_difTol, PFDR_itMax, verbose=0, time=False,
+                                         obj=False, dif=False):
+    """octave/mex/CP_PFDR_graph_quadratic_d1_l1_duplex_mex.cpp: cut pursuit for
+    1/2 ||y - A x||^2 + sum_e La_d1 |x_u - x_v| + sum_v La_l1 |x_v| (x >= 0 with
+    positivity), A N-by-V, one two-layer cut per iteration, the whole loop on
+    the GPU (pfdr_cp_quadratic_d1_l1_duplex).  La_l1: array, scalar or None.
+    Returns (Cv, rX, CP_it, Time, Obj, Dif): the component of every vertex
+    (int32[V]), the value of every component -- the minimiser is rX[Cv] -- and
+    the records asked for (None otherwise)."""
+    A = np.asarray(A)
+    dt = np.result_type(Y, np.float32)
+    N, V = A.shape
+    return _cp_duplex(V, N, np.asarray(Y, dt).ravel(), np.asfortranarray(A, dt).ravel(order="F"),
+                      Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, PFDR_rho,
+                      PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+
+
+def CP_PFDR_graph_l22_d1_l1_duplex(Y, La_l2, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
+                                   CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
+                                   PFDR_itMax, verbose=0, time=False, obj=False, dif=False):
+    """octave/mex/CP_PFDR_graph_l22_d1_l1_duplex_mex.cpp:66-93: Y <- La_l2*Y,
+    N = 0, A = La_l2 (diagonal; a scalar: none); Obj += 1/2 ||y||^2_La_l2."""
+    Y = np.asarray(Y).ravel()
+    dt = np.result_type(Y, np.float32)
+    V = Y.size
+    La_l2 = _scal_or_vec(La_l2, V, dt)
+    Yw = (La_l2 * Y).astype(dt) if La_l2 is not None else Y.astype(dt)
+    Cv, rX, it, Time, Obj, Dif = _cp_duplex(
+        V, 0, Yw, La_l2, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, PFDR_rho,
+        PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+    if Obj is not None:
+        y = Y.astype(dt)
+        w = La_l2 if La_l2 is not None else np.ones(V, dt)
+        Obj[: it + 1] += float(np.sum(w.astype(np.float64) * y * y)) / 2.0
+    return Cv, rX, it, Time, Obj, Dif
+
+
 def _binding_inputs(obs, source, target, edge_weight, A, l1_weight):
     """the input conventions of the reference's Python binding (see
     PFDR_quadratic_l1) -> (dtype, N, V, mode, A, obs, Eu, Ev, edge weights[E],
@@ -682,6 +756,29 @@ def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0
     else:
         r = lib.cp_quadratic_d1_l1(V, N, obs, np.asfortranarray(A).ravel(order="F"), Eu, Ev, ew,
                                    lw, **kw)
+    return r[0].astype(np.uint32), r[1]
+
+
+def CP_quadratic_l1_duplex(obs, source, target, edge_weight, A, l1_weight, positivity=0,
+                           PFDR_rho=1.0, PFDR_condMin=1e-3, CP_difTol=1e-3, PFDR_difRcd=0.0,
+                           PFDR_difTol=1e-4, CP_itMax=10, PFDR_itMax=10000, verbose=0):
+    """CP_quadratic_l1 through the duplex driver (one two-layer cut per
+    iteration, pfdr_cp_quadratic_d1_l1_duplex): same signature, defaults, input
+    conventions and returns."""
+    dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
+                                                             A, l1_weight)
+    lib = Lib()
+    kw = dict(positivity=positivity, CP_difTol=CP_difTol, CP_itMax=CP_itMax, rho=PFDR_rho,
+              condMin=PFDR_condMin, difRcd=PFDR_difRcd, difTol=PFDR_difTol, itMax=PFDR_itMax,
+              verbose=verbose)
+    if mode == "identity":
+        r = lib.cp_quadratic_d1_l1_duplex(V, 0, obs, None, Eu, Ev, ew, lw, **kw)
+    elif mode == "diagonal":
+        r = lib.cp_quadratic_d1_l1_duplex(V, 0, (obs * A).astype(dt), (A * A).astype(dt), Eu, Ev,
+                                          ew, lw, **kw)
+    else:
+        r = lib.cp_quadratic_d1_l1_duplex(V, N, obs, np.asfortranarray(A).ravel(order="F"), Eu,
+                                          Ev, ew, lw, **kw)
     return r[0].astype(np.uint32), r[1]
 
 
@@ -1127,8 +1224,26 @@ class CPGraph:
                    C.byref(flow), C.byref(rounds))
         return seg, flow.value, rounds.value
 
+    def mincut_duplex(self, tr_cap, r_link, r_cap):
+        """minimum cut of the two-layer network ``capacities_duplex`` gives
+        (node v and node V + v per vertex) -> (segment[2V] uint8: 0 = reachable
+        from the source in the residual graph, the reference's maxflow labels;
+        cut value; push/relabel rounds)"""
+        tr = np.ascontiguousarray(tr_cap, self.dtype)
+        ln = np.ascontiguousarray(r_link, self.dtype)
+        rc = np.ascontiguousarray(r_cap, self.dtype)
+        if tr.size != 2 * self.V or ln.size != self.V or rc.size != self.E:
+            raise ValueError("mincut_duplex: tr_cap must have 2V, r_link V and r_cap E entries")
+        seg = np.empty(2 * self.V, np.uint8)
+        flow = C.c_double()
+        rounds = C.c_int64()
+        self._call("pfdr_cpgraph_mincut_duplex", self._p(tr), self._p(ln),
+                   self._p(rc) if self.E else None, PFDR_MEM_HOST, self._p(seg),
+                   C.byref(flow), C.byref(rounds))
+        return seg, flow.value, rounds.value
+
     def mincut_relabels(self):
-        """global relabels of the last ``mincut``"""
+        """global relabels of the last ``mincut`` or ``mincut_duplex``"""
         n = C.c_int64()
         self._call("pfdr_cpgraph_mincut_relabels", C.byref(n))
         return n.value

@@ -420,6 +420,23 @@ int pfdr_cpgraph_capacities_duplex(pfdr_cpgraph *g, int positivity, void *tr_cap
     void *r_link, void *r_cap, int mem);
 int pfdr_cpgraph_activate_duplex(pfdr_cpgraph *g, const uint8_t *segment, int mem,
     int *activated);
+/* The duplex driver's cut.  Node v (v1) and node V + v (v2) per vertex;
+ * tr_cap[2V] (> 0 source, < 0 sink, may be infinite), r_link[V]: arc v1 -> v2
+ * (v2 -> v1 has none), r_cap[E]: both arcs of edge e in both layers; finite,
+ * >= 0.  segment[2V]: 0 = SOURCE exactly for the nodes reachable from the
+ * source in the residual graph of a maximum flow (the reference's BK answer
+ * on the graph of :101-116), 1 = SINK.  pfdr_cpgraph_mincut's contract
+ * otherwise: host or device memory per mem, the same bytes on every run, flow
+ * (the cut's value: terminals, r_cap once per layer, links) summed in f64 in
+ * a fixed order, flow and rounds optional, only the endpoints are read.  The
+ * rounds are pfdr_cpgraph_mincut's own kernels over a CSR of 2V nodes and
+ * 2E + V edges, built by the graph's first two-layer cut and kept with it.
+ * A NaN terminal, a negative, NaN or infinite r_cap or r_link, or
+ * 2 (2E + V) > INT_MAX (the CSR's offsets are int): PFDR_ERR_ARG.
+ * pfdr_cpgraph_mincut_relabels reports the last cut of either kind. */
+int pfdr_cpgraph_mincut_duplex(pfdr_cpgraph *g, const void *tr_cap, const void *r_link,
+                               const void *r_cap, int mem, uint8_t *segment,
+                               double *flow, int64_t *rounds);
 
 /* The simplex driver, CP_PFDR_graph_loss_d1_simplex (graph created
  * without La_l1): K >= 2 labels, Q[V*K] and the component label vectors
@@ -478,6 +495,42 @@ int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv, double *r
     const double *La_l1, int positivity, double CP_difTol, int CP_itMax, int *CP_it,
     double rho, double condMin, double difRcd, double difTol, int itMax,
     double *Time, double *Obj, double *Dif, int verbose);
+
+/* CP_PFDR_graph_quadratic_d1_l1_duplex<real> of the reference (arguments as
+ * include/CP_PFDR_graph_quadratic_d1_l1.hpp:133-142, without the restart
+ * record): pfdr_cp_quadratic_d1_l1's loop with one two-layer cut per
+ * iteration in place of its two cuts -- gradient,
+ * pfdr_cpgraph_capacities_duplex, pfdr_cpgraph_mincut_duplex,
+ * pfdr_cpgraph_activate_duplex -- and everything else (initialisation, eps,
+ * the iteration that activates nothing, the reduced problem, PFDR from zero,
+ * merge, residual, iterate evolution, objective, stopping rule, argument
+ * checks, NULL outputs) that entry's, resident on the device in the same way.
+ * Two corners the reference leaves undefined:
+ *  - differentiable case (no La_l1, no positivity): the reference builds the
+ *    one-layer graph but indexes it as if it had four arcs per edge (:407,
+ *    :628, :869); not reproduced.  The entry runs the l1 driver's single-cut
+ *    path: the result equals pfdr_cp_quadratic_d1_l1's byte for byte.
+ *  - positivity without La_l1: the reference reads the up / down directional
+ *    derivatives from uninitialised memory (:470-502); here both are the
+ *    gradient (pfdr_cpgraph_capacities_duplex).
+ * verbose prints what pfdr_cp_quadratic_d1_l1 prints. */
+int pfdr_cp_quadratic_d1_l1_duplex_f32(int V, int E, int N, int *rV, int *Cv, float *rX,
+    const float *Y, const float *A, const int *Eu, const int *Ev, const float *La_d1,
+    const float *La_l1, int positivity, float CP_difTol, int CP_itMax, int *CP_it,
+    float rho, float condMin, float difRcd, float difTol, int itMax,
+    double *Time, float *Obj, float *Dif, int verbose);
+int pfdr_cp_quadratic_d1_l1_duplex_f64(int V, int E, int N, int *rV, int *Cv, double *rX,
+    const double *Y, const double *A, const int *Eu, const int *Ev, const double *La_d1,
+    const double *La_l1, int positivity, double CP_difTol, int CP_itMax, int *CP_it,
+    double rho, double condMin, double difRcd, double difTol, int itMax,
+    double *Time, double *Obj, double *Dif, int verbose);
+/* Where the calling thread's last pfdr_cp_quadratic_d1_l1_duplex_* call spent
+ * its time; the layout of pfdr_cp_quadratic_d1_bounds_stats: seconds[6] =
+ * gradient, the cuts (capacities, cut, activation), the other graph steps and
+ * the reduction, PFDR, the evolution / objective sums, the whole call;
+ * counts[4] = cuts, push/relabel rounds, global relabels, PFDR iterations.
+ * Either output may be NULL. */
+int pfdr_cp_quadratic_d1_l1_duplex_stats(double *seconds, int64_t *counts);
 
 /* CP_PFDR_graph_quadratic_d1_bounds<real> of the reference (arguments as
  * include/CP_PFDR_graph_quadratic_d1_bounds.hpp, without the restart record):
