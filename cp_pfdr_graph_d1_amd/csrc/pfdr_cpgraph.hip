@@ -1127,6 +1127,7 @@ struct CpGraphBase {
     virtual void capacities_bounds(int cut, double mn, double mx, void *tr, void *rc,
                                    int mem) = 0;
     virtual void set_values(const void *rX, int mem) = 0;
+    virtual void set_weights(const void *La_d1, const void *La_l1, int mem) = 0;
     virtual void get_reduced(int *rEu_o, int *rEv_o, void *rLa_o, void *rL1_o, int mem) = 0;
     virtual void get_dfs(void *out, int mem) = 0;
     int activate(const uint8_t *seg, int mem);
@@ -1316,6 +1317,13 @@ struct CpGraph : CpGraphBase {
         if (rV <= 0) throw std::runtime_error("set_values: no components");
         rX.alloc(rV);
         PFDR_HIP(hipMemcpyAsync(rX.p, x, sizeof(real) * rV, kind_in(mem), s));
+        PFDR_HIP(hipStreamSynchronize(s));
+    }
+
+    void set_weights(const void *la, const void *l1, int mem) override {
+        if (l1 && !has_l1) throw std::runtime_error("set_weights: the graph has no La_l1");
+        if (la && E > 0) PFDR_HIP(hipMemcpyAsync(La.p, la, sizeof(real) * E, kind_in(mem), s));
+        if (l1) PFDR_HIP(hipMemcpyAsync(L1.p, l1, sizeof(real) * V, kind_in(mem), s));
         PFDR_HIP(hipStreamSynchronize(s));
     }
 
@@ -1809,6 +1817,35 @@ extern "C" int pfdr_cpgraph_set_active(pfdr_cpgraph *h, const uint8_t *active, i
     })
 }
 
+// active[e] = the ends of e carry different labels
+__global__ void k_cp_active_by_labels(long E, const int *__restrict__ Eu,
+                                      const int *__restrict__ Ev, const int *__restrict__ label,
+                                      uint8_t *__restrict__ active) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    active[e] = label[Eu[e]] != label[Ev[e]];
+}
+
+static void cpg_active_by_labels(pfdr::CpGraphBase *g, const int *label, int mem) {
+    pfdr::DevBuf<int> bl;
+    const int *dl = label;
+    if (mem != PFDR_MEM_DEVICE) {
+        bl.alloc(g->V);
+        PFDR_HIP(hipMemcpyAsync(bl.p, label, sizeof(int) * g->V, hipMemcpyHostToDevice, g->s));
+        dl = bl.p;
+    }
+    if (g->E > 0)
+        k_cp_active_by_labels<<<pfdr::grid_for(g->E), pfdr::kBlock, 0, g->s>>>(
+            g->E, g->Eu.p, g->Ev.p, dl, g->active.p);
+    PFDR_HIP(hipGetLastError());
+    PFDR_HIP(hipStreamSynchronize(g->s));
+}
+
+extern "C" int pfdr_cpgraph_set_active_by_labels(pfdr_cpgraph *h, const int *label, int mem) {
+    if (!h || !label) return report_error("pfdr_cpgraph_set_active_by_labels", "null argument");
+    CPG_TRY("pfdr_cpgraph_set_active_by_labels", cpg_active_by_labels(h->g, label, mem))
+}
+
 extern "C" int pfdr_cpgraph_get_active(pfdr_cpgraph *h, uint8_t *active, int mem) {
     if (!h || !active) return report_error("pfdr_cpgraph_get_active", "null argument");
     CPG_TRY("pfdr_cpgraph_get_active", {
@@ -1852,6 +1889,12 @@ extern "C" int pfdr_cpgraph_get_components(pfdr_cpgraph *h, int *rV, int *Cv, in
 extern "C" int pfdr_cpgraph_set_values(pfdr_cpgraph *h, const void *rX, int mem) {
     if (!h || !rX) return report_error("pfdr_cpgraph_set_values", "null argument");
     CPG_TRY("pfdr_cpgraph_set_values", h->g->set_values(rX, mem))
+}
+
+extern "C" int pfdr_cpgraph_set_weights(pfdr_cpgraph *h, const void *La_d1, const void *La_l1,
+                                        int mem) {
+    if (!h) return report_error("pfdr_cpgraph_set_weights", "null graph");
+    CPG_TRY("pfdr_cpgraph_set_weights", h->g->set_weights(La_d1, La_l1, mem))
 }
 
 extern "C" int pfdr_cpgraph_components(pfdr_cpgraph *h, int *rV) {

@@ -13,25 +13,22 @@
 // The scalar sums (initialize :94-136, the iterate evolution :905-923 and the
 // objective :927-975) are added one by one in `real` in the reference's
 // order (ordered_segment_sums), like the reference built without OpenMP.
+//
+// The driver runs in three phases (pfdr_cp_driver.hpp): setup (upload, graph,
+// the reference's initialize()), the loop from the state the driver holds, and
+// the download.  An entry is the three in a row; the resumable solver
+// (pfdr_cp_solver.hip) keeps the driver and runs the same loop again.
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <stdexcept>
 #include <vector>
 
-#include "pfdr_graph.hpp"
+#include "pfdr_cp_driver.hpp"
 
 namespace pfdr {
 
 namespace {
-
-struct AbiFail {  // a library call failed: its message is already recorded
-    int status;
-};
-#define CP_ABI(call)                               \
-    do {                                           \
-        const int st_ = (call);                    \
-        if (st_ != PFDR_OK) throw AbiFail{st_};    \
-    } while (0)
 
 // What a call spent where (pfdr_cp_quadratic_d1_l1_duplex_stats: the last
 // duplex call on this thread).
@@ -121,13 +118,21 @@ __global__ void k_cpq_obj_l1(int rV, const real *__restrict__ rL1, const real *_
 // which differs from the l1 driver in the graph and the cut only: one
 // two-layer cut per iteration when there is an l1 term or positivity
 template <typename real>
-struct Driver {
-    using clock = std::chrono::steady_clock;
-    hipStream_t s = lib_stream();
+struct Driver : CpDriverBase {
     bool duplex = false;
     Stats st;  // of the last run
     DevBuf<int> off{2};
     DevBuf<real> one{1};
+    // the resident problem
+    DevBuf<real> dY, dA;
+    const real *pA = nullptr;  // dA, or the caller's device A
+    int positivity = 0;
+    // the state besides the graph's: values, Cv, residual (N > 0)
+    DevBuf<real> drX, dR;
+    DevBuf<int> dCv, dVc, drVc;
+    std::vector<real> hR;  // N > 0: the residual's host mirror
+    real obj = real(0);    // the functional at the state, when known
+    bool obj_known = false;
 
     static double since(clock::time_point t) {
         return std::chrono::duration<double>(clock::now() - t).count();
@@ -152,52 +157,46 @@ struct Driver {
         if (n) hp.copy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice);
     }
 
-    void run(int V, int E, int N, int *rV_out, int *Cv, real *rX_out, const real *Y,
-             const real *A, const int *Eu, const int *Ev, const real *La_d1, const real *La_l1,
-             int positivity, real CP_difTol, int CP_itMax, int *CP_it_out, real rho,
-             real condMin, real difRcd, real difTol, int itMax, double *Time, real *Obj,
-             real *Dif, int verbose) {
-        const auto t0 = clock::now();
-        auto t = t0;
-        st = Stats{};
-        const bool two = duplex && (La_l1 || positivity);  // the two-layer cut
+    void setup(const pfdr_cp_problem &p, bool want_obj) override {
+        V = p.V, E = p.E, N = p.N;
+        positivity = p.positivity;
+        has_l1 = p.La_l1 != nullptr;
+        const real *Y = (const real *)p.Y, *A = (const real *)p.A;
         const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
-        const real eps = (real(0) < CP_difTol && CP_difTol < Lim<real>::eps) ? CP_difTol
-                                                                            : Lim<real>::eps;
-        const int gV = grid_for(V);
+        const bool dev = p.mem == PFDR_MEM_DEVICE;
         // ---- the problem, once, into HBM
-        DevBuf<real> dY, dA, dLa, dL1;
+        DevBuf<real> dLa, dL1;
         DevBuf<int> dEu, dEv;
         {
             HostPins hp(s);
             const size_t asz = N > 0 ? (size_t)N * V : N < 0 ? (size_t)V * V : A ? (size_t)V : 0;
-            up(dY, Y, N > 0 ? (size_t)N : (size_t)V, hp);
-            up(dA, A, asz, hp);
-            up(dEu, Eu, (size_t)E, hp);
-            up(dEv, Ev, (size_t)E, hp);
-            up(dLa, La_d1, (size_t)E, hp);
-            if (La_l1) up(dL1, La_l1, (size_t)V, hp);
+            cp_take(dY, Y, N > 0 ? (size_t)N : (size_t)V, p.mem, hp, s);
+            if (!dev) up(dA, A, asz, hp);
+            cp_take(dEu, p.Eu, (size_t)E, p.mem, hp, s);
+            cp_take(dEv, p.Ev, (size_t)E, p.mem, hp, s);
+            cp_take(dLa, (const real *)p.La_d1, (size_t)E, p.mem, hp, s);
+            if (has_l1) cp_take(dL1, (const real *)p.La_l1, (size_t)V, p.mem, hp, s);
             hp.release();
         }
-        const real *pA = A ? dA.p : nullptr;
-        pfdr_cpgraph *g = nullptr;
-        CP_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, La_l1 ? dL1.p : nullptr,
+        pA = !A ? nullptr : dev ? A : dA.p;
+        CP_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, has_l1 ? dL1.p : nullptr,
                                    PFDR_MEM_DEVICE));
-        struct Hold {
-            pfdr_cpgraph *g;
-            ~Hold() { pfdr_cpgraph_destroy(g); }
-        } hold{g};
 
         // ---- initialize (:94-175): the one-component solution
-        std::vector<real> hR, hY;  // N > 0: residual and observations (N-sized)
-        DevBuf<real> dR;
+        std::vector<real> hY;  // N > 0: the observations (N-sized)
         real rY = real(0), rAA = real(0), rL1s = real(0);
         if (N > 0) {
             DevBuf<real> drA(N);
-            k_cpq_colsum<real><<<grid_for(N), kBlock, 0, s>>>(N, V, dA.p, drA.p);
+            k_cpq_colsum<real><<<grid_for(N), kBlock, 0, s>>>(N, V, pA, drA.p);
             PFDR_HIP(hipGetLastError());
             hR.resize(N);
-            hY.assign(Y, Y + N);
+            if (dev) {
+                hY.resize(N);
+                PFDR_HIP(hipMemcpyAsync(hY.data(), dY.p, sizeof(real) * N, hipMemcpyDeviceToHost,
+                                        s));
+            } else {
+                hY.assign(Y, Y + N);
+            }
             PFDR_HIP(hipMemcpyAsync(hR.data(), drA.p, sizeof(real) * N, hipMemcpyDeviceToHost, s));
             PFDR_HIP(hipStreamSynchronize(s));
             for (int n = 0; n < N; n++) {
@@ -206,16 +205,16 @@ struct Driver {
             }
         } else {
             rY = seq_sum(dY.p, V);
-            if (N < 0) rAA = seq_sum(dA.p, (long)V * V);
-            else if (A) rAA = seq_sum(dA.p, V);
+            if (N < 0) rAA = seq_sum(pA, (long)V * V);
+            else if (A) rAA = seq_sum(pA, V);
             else rAA = (real)V;
         }
-        if (La_l1) rL1s = seq_sum(dL1.p, V);
+        if (has_l1) rL1s = seq_sum(dL1.p, V);
         real x0 = real(0);
         if (rY > rL1s) x0 = (rY - rL1s) / rAA;
         else if (!positivity && rY < -rL1s) x0 = (rY + rL1s) / rAA;
-        int rV = 1, rE = 0;
-        DevBuf<real> drX(1);
+        rV = 1;
+        drX.alloc(1);
         PFDR_HIP(hipMemcpyAsync(drX.p, &x0, sizeof(real), hipMemcpyHostToDevice, s));
         PFDR_HIP(hipStreamSynchronize(s));
         CP_ABI(pfdr_cpgraph_set_values(g, drX.p, PFDR_MEM_DEVICE));
@@ -225,7 +224,8 @@ struct Driver {
             PFDR_HIP(hipMemcpyAsync(dR.p, hR.data(), sizeof(real) * N, hipMemcpyHostToDevice, s));
             PFDR_HIP(hipStreamSynchronize(s));
         }
-        if (Obj) {
+        obj_known = false;
+        if (want_obj) {
             real a = real(0);
             if (N > 0) {
                 for (int n = 0; n < N; n++) a += hR[n] * hR[n];
@@ -233,24 +233,97 @@ struct Driver {
             } else {
                 a = x0 * (real(0.5) * rAA * x0 - rY);
             }
-            Obj[0] = a;
-            if (La_l1) Obj[0] += rL1s * (x0 < real(0) ? -x0 : x0);
+            obj = a;
+            if (has_l1) obj += rL1s * (x0 < real(0) ? -x0 : x0);
+            obj_known = true;
         }
+        dCv.alloc(V);
+        dVc.alloc(V);
+        drVc.alloc((size_t)V + 1);
+        CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+    }
+
+    // R = Y - A X at the graph's components and drX (:889-901): the component
+    // column sums of pfdr_cp_reduce, then k_cpq_residual, as the loop does
+    void residual_from_state() {
+        CP_ABI(pfdr_cpgraph_get_components(g, nullptr, nullptr, dVc.p, drVc.p, PFDR_MEM_DEVICE));
+        DevBuf<real> rA((size_t)N * rV), L(rV);
+        if (sizeof(real) == 4)
+            CP_ABI(pfdr_cp_reduce_f32(N, V, (const float *)pA, (const float *)dY.p, rV, drVc.p,
+                                      dVc.p, 0, PFDR_MEM_DEVICE, 1e-3f, 100, 10, (float *)rA.p,
+                                      nullptr, nullptr, (float *)L.p, nullptr));
+        else
+            CP_ABI(pfdr_cp_reduce_f64(N, V, (const double *)pA, (const double *)dY.p, rV, drVc.p,
+                                      dVc.p, 0, PFDR_MEM_DEVICE, 1e-3, 100, 10, (double *)rA.p,
+                                      nullptr, nullptr, (double *)L.p, nullptr));
+        k_cpq_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rV, rA.p, drX.p, dY.p, dR.p);
+        PFDR_HIP(hipGetLastError());
+        PFDR_HIP(hipStreamSynchronize(s));
+    }
+
+    void adopt(int rV_new, const void *x, const void *R) override {
+        rV = rV_new;
+        drX.alloc(rV);
+        PFDR_HIP(hipMemcpyAsync(drX.p, x, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+        CP_ABI(pfdr_cpgraph_set_values(g, drX.p, PFDR_MEM_DEVICE));
+        CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+        if (N > 0) {
+            if (R) {
+                PFDR_HIP(hipMemcpyAsync(dR.p, R, sizeof(real) * N, hipMemcpyDeviceToDevice, s));
+                PFDR_HIP(hipStreamSynchronize(s));
+            } else {
+                residual_from_state();
+            }
+        }
+        obj_known = false;
+    }
+    const void *values() const override { return drX.p; }
+    const void *residual() const override { return N > 0 ? dR.p : nullptr; }
+    void forget_objective() override { obj_known = false; }
+    void stats(double *seconds, int64_t *counts) const override {
+        if (seconds) {
+            const double v[6] = {st.gradient, st.cuts, st.graph, st.pfdr, st.sums, st.total};
+            for (int i = 0; i < 6; i++) seconds[i] = v[i];
+        }
+        if (counts) {
+            counts[0] = st.ncuts;
+            counts[1] = st.rounds;
+            counts[2] = st.relabels;
+            counts[3] = st.pfdr_it;
+        }
+    }
+
+    void loop(clock::time_point t0, const pfdr_cp_params &q, int *CP_it_out, double *Time,
+              void *Obj_, void *Dif_) override {
+        const real CP_difTol = (real)q.CP_difTol, rho = (real)q.rho, condMin = (real)q.condMin,
+                   difRcd = (real)q.difRcd, difTol = (real)q.difTol;
+        const int CP_itMax = q.CP_itMax, itMax = q.itMax, verbose = q.verbose;
+        real *Obj = (real *)Obj_, *Dif = (real *)Dif_;
+        auto t = t0;
+        st = Stats{};
+        const bool two = duplex && (has_l1 || positivity);  // the two-layer cut
+        const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
+        const real eps = (real(0) < CP_difTol && CP_difTol < Lim<real>::eps) ? CP_difTol
+                                                                            : Lim<real>::eps;
+        const int gV = grid_for(V);
+        const bool La_l1 = has_l1;
+        int rE = 0;  // a restart reports no reduced edge before its first iteration
+        if (Obj) Obj[0] = obj_known ? obj : std::numeric_limits<real>::quiet_NaN();
 
         // ---- cut pursuit
-        DevBuf<int> dCv(V), dVc(V), drVc((size_t)V + 1), dCv_;
+        DevBuf<int> dCv_;
         const size_t nodes = two ? 2 * (size_t)V : (size_t)V;  // of the cut's network
         DevBuf<real> drX_, dtr(nodes), drc(E > 0 ? E : 1), dlink, t1, t2;
         DevBuf<uint8_t> dseg(nodes);
         if (two) dlink.alloc(V);
-        CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
         const bool track = CP_difTol > real(0) || Dif;
         if (track) {
-            drX_.alloc(1);
+            drX_.alloc(rV);
             dCv_.alloc(V);
             t1.alloc(V);
             t2.alloc(V);
-            PFDR_HIP(hipMemcpyAsync(drX_.p, drX.p, sizeof(real), hipMemcpyDeviceToDevice, s));
+            PFDR_HIP(hipMemcpyAsync(drX_.p, drX.p, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
             PFDR_HIP(hipMemcpyAsync(dCv_.p, dCv.p, sizeof(int) * V, hipMemcpyDeviceToDevice, s));
             PFDR_HIP(hipStreamSynchronize(s));
         }
@@ -382,7 +455,7 @@ struct Driver {
                 CP_ABI(pfdr_session_run(ses, itMax, &pit));
                 CP_ABI(pfdr_session_sync(ses));
                 const void *x = pfdr_session_device_x(ses);
-                if (!x) throw AbiFail{PFDR_ERR_STATE};
+                if (!x) throw CpAbiFail{PFDR_ERR_STATE};
                 PFDR_HIP(hipMemcpyAsync(drX.p, x, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
                 PFDR_HIP(hipStreamSynchronize(s));
             }
@@ -439,18 +512,22 @@ struct Driver {
                     PFDR_HIP(hipGetLastError());
                     Obj[it] += seq_sum(t.p, rV);
                 }
+                obj = Obj[it];
             }
+            obj_known = Obj != nullptr;
             PFDR_HIP(hipStreamSynchronize(s));  // the iteration's buffers leave scope
             st.sums += since(t);
         }
-        // ---- the result
-        *rV_out = rV;
         if (CP_it_out) *CP_it_out = it;
+        st.total = since(t0);
+    }
+
+    void download(int *rV_out, int *Cv, void *rX_out) override {
+        *rV_out = rV;
         HostPins hp(s);
         hp.copy(Cv, dCv.p, sizeof(int) * V, hipMemcpyDeviceToHost);
         hp.copy(rX_out, drX.p, sizeof(real) * rV, hipMemcpyDeviceToHost);
         hp.release();
-        st.total = since(t0);
     }
 };
 
@@ -466,6 +543,7 @@ int cp_entry(const char *fn, bool duplex, int V, int E, int N, int *rV, int *Cv,
     if (N != 0 && !A) return report_error(fn, "N != 0 needs A");
     if (N < 0 && -N != V) return report_error(fn, "N < 0 needs A = A^tA and N = -V");
     try {
+        const auto t0 = std::chrono::steady_clock::now();
         Driver<real> d;
         d.duplex = duplex;
         struct Keep {  // what the call spent, also when it fails half way
@@ -474,9 +552,19 @@ int cp_entry(const char *fn, bool duplex, int V, int E, int N, int *rV, int *Cv,
                 if (d.duplex) g_duplex_stats = d.st;
             }
         } keep{d};
-        d.run(V, E, N, rV, Cv, rX, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax,
-              CP_it, rho, condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
-    } catch (const AbiFail &f) {
+        pfdr_cp_problem p{};
+        p.kind = PFDR_KIND_L1;
+        p.duplex = duplex;
+        p.mem = PFDR_MEM_HOST;
+        p.V = V, p.E = E, p.N = N;
+        p.Y = Y, p.A = A, p.Eu = Eu, p.Ev = Ev, p.La_d1 = La_d1, p.La_l1 = La_l1;
+        p.positivity = positivity;
+        const pfdr_cp_params q{CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose};
+        d.setup(p, Obj != nullptr);
+        d.loop(t0, q, CP_it, Time, Obj, Dif);
+        d.download(rV, Cv, rX);
+        d.st.total = Driver<real>::since(t0);
+    } catch (const CpAbiFail &f) {
         return f.status;
     } catch (const HipError &h) {
         return report_error(fn, h);
@@ -487,6 +575,17 @@ int cp_entry(const char *fn, bool duplex, int V, int E, int N, int *rV, int *Cv,
 }
 
 }  // namespace
+
+CpDriverBase *cp_make_l1_driver(int dtype, bool duplex) {
+    if (dtype == PFDR_F32) {
+        auto *d = new Driver<float>();
+        d->duplex = duplex;
+        return d;
+    }
+    auto *d = new Driver<double>();
+    d->duplex = duplex;
+    return d;
+}
 
 }  // namespace pfdr
 

@@ -17,24 +17,23 @@
 //
 // One departure from the reference: min > max or a NaN bound is an
 // argument error (the reference clamps to min and hands PFDR an empty box).
+//
+// The driver runs in three phases (pfdr_cp_driver.hpp): setup (upload, graph,
+// the reference's initialize()), the loop from the state the driver holds, and
+// the download.  An entry is the three in a row; the resumable solver
+// (pfdr_cp_solver.hip) keeps the driver and runs the same loop again.
 #include <algorithm>
 #include <chrono>
+#include <limits>
 #include <stdexcept>
 
-#include "pfdr_graph.hpp"
+#include "pfdr_cp_driver.hpp"
 
 namespace pfdr {
 
 namespace {
 
-struct AbiFail {  // a library call failed: its message is already recorded
-    int status;
-};
-#define CPB_ABI(call)                              \
-    do {                                           \
-        const int st_ = (call);                    \
-        if (st_ != PFDR_OK) throw AbiFail{st_};    \
-    } while (0)
+#define CPB_ABI(call) CP_ABI(call)
 
 // What the last call on this thread spent where (pfdr_cp_quadratic_d1_bounds_stats).
 struct Stats {
@@ -148,11 +147,19 @@ __global__ void k_cpb_obj_d1(int rE, const int *__restrict__ rEu, const int *__r
 }
 
 template <typename real>
-struct BdDriver {
-    using clock = std::chrono::steady_clock;
-    hipStream_t s = lib_stream();
+struct BdDriver : CpDriverBase {
+    Stats st;  // of the last run
     DevBuf<int> off{2};
     DevBuf<real> one{1};
+    // the resident problem
+    DevBuf<real> dY, dA;
+    const real *pA = nullptr;  // dA, or the caller's device A
+    real min = real(0), max = real(0);
+    // the state besides the graph's: values, Cv, residual (N > 0)
+    DevBuf<real> drX, dR, dtN;  // dtN: the terms of the residual's sums
+    DevBuf<int> dCv, dVc, drVc;
+    real obj = real(0);  // the functional at the state, when known
+    bool obj_known = false;
 
     // ((0 + x[0]) + x[1]) + ... in real
     real seq_sum(const real *x, long n) {
@@ -186,49 +193,37 @@ struct BdDriver {
         return a;
     }
 
-    void run(int V, int E, int N, int *rV_out, int *Cv, real *rX_out, const real *Y,
-             const real *A, const int *Eu, const int *Ev, const real *La_d1, real min, real max,
-             real CP_difTol, int CP_itMax, int *CP_it_out, real rho, real condMin, real difRcd,
-             real difTol, int itMax, double *Time, real *Obj, real *Dif, int verbose) {
-        const auto t0 = clock::now();
-        Stats &st = g_stats;
-        st = Stats{};
+    void setup(const pfdr_cp_problem &p, bool want_obj) override {
+        V = p.V, E = p.E, N = p.N;
+        min = (real)p.min, max = (real)p.max;
+        const real *Y = (const real *)p.Y, *A = (const real *)p.A;
         const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
-        const real eps = (real(0) < CP_difTol && CP_difTol < Lim<real>::eps) ? CP_difTol
-                                                                            : Lim<real>::eps;
-        const real inf = Lim<real>::huge;
-        const int gV = grid_for(V);
+        const bool dev = p.mem == PFDR_MEM_DEVICE;
         // ---- the problem, once, into HBM
-        DevBuf<real> dY, dA, dLa;
+        DevBuf<real> dLa;
         DevBuf<int> dEu, dEv;
         {
             HostPins hp(s);
             const size_t asz = N > 0 ? (size_t)N * V : N < 0 ? (size_t)V * V : A ? (size_t)V : 0;
-            up(dY, Y, N > 0 ? (size_t)N : (size_t)V, hp);
-            up(dA, A, asz, hp);
-            up(dEu, Eu, (size_t)E, hp);
-            up(dEv, Ev, (size_t)E, hp);
-            up(dLa, La_d1, (size_t)E, hp);
+            cp_take(dY, Y, N > 0 ? (size_t)N : (size_t)V, p.mem, hp, s);
+            if (!dev) up(dA, A, asz, hp);
+            cp_take(dEu, p.Eu, (size_t)E, p.mem, hp, s);
+            cp_take(dEv, p.Ev, (size_t)E, p.mem, hp, s);
+            cp_take(dLa, (const real *)p.La_d1, (size_t)E, p.mem, hp, s);
             hp.release();
         }
-        const real *pA = A ? dA.p : nullptr;
-        pfdr_cpgraph *g = nullptr;
+        pA = !A ? nullptr : dev ? A : dA.p;
         CPB_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, nullptr, PFDR_MEM_DEVICE));
-        struct Hold {
-            pfdr_cpgraph *g;
-            ~Hold() { pfdr_cpgraph_destroy(g); }
-        } hold{g};
 
         // ---- initialize (:66-170): the one-component solution, projected on the box
         auto t = clock::now();
-        DevBuf<real> dR, dtN;  // N > 0: the residual and the terms of its sums
         real rY = real(0), rAA = real(0);
         DevBuf<real> drA0;
         if (N > 0) {
             drA0.alloc(N);
             dtN.alloc(N);
             dR.alloc(N);
-            k_cpb_colsum<real><<<grid_for(N), kBlock, 0, s>>>(N, V, dA.p, drA0.p);
+            k_cpb_colsum<real><<<grid_for(N), kBlock, 0, s>>>(N, V, pA, drA0.p);
             k_cpb_init_products<real><<<grid_for(N), kBlock, 0, s>>>(N, drA0.p, dY.p, dtN.p,
                                                                     dR.p);
             PFDR_HIP(hipGetLastError());
@@ -236,15 +231,15 @@ struct BdDriver {
             rAA = seq_sum(dR.p, N);
         } else {
             rY = seq_sum(dY.p, V);
-            if (N < 0) rAA = seq_sum(dA.p, (long)V * V);
-            else if (A) rAA = seq_sum(dA.p, V);
+            if (N < 0) rAA = seq_sum(pA, (long)V * V);
+            else if (A) rAA = seq_sum(pA, V);
             else rAA = (real)V;
         }
         real x0 = rY / rAA;
         if (x0 < min) x0 = min;  // :138-139
         else if (x0 > max) x0 = max;
-        int rV = 1, rE = 0;
-        DevBuf<real> drX(1);
+        rV = 1;
+        drX.alloc(1);
         PFDR_HIP(hipMemcpyAsync(drX.p, &x0, sizeof(real), hipMemcpyHostToDevice, s));
         PFDR_HIP(hipStreamSynchronize(s));
         CPB_ABI(pfdr_cpgraph_set_values(g, drX.p, PFDR_MEM_DEVICE));
@@ -252,25 +247,98 @@ struct BdDriver {
             k_cpb_init_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, drA0.p, dY.p, x0, dR.p);
             PFDR_HIP(hipGetLastError());
         }
-        if (Obj) {
-            if (N > 0) Obj[0] = half_norm2(N, dR.p, dtN.p);
-            else Obj[0] = x0 * (real(0.5) * rAA * x0 - rY);
+        obj_known = false;
+        if (want_obj) {
+            if (N > 0) obj = half_norm2(N, dR.p, dtN.p);
+            else obj = x0 * (real(0.5) * rAA * x0 - rY);
+            obj_known = true;
         }
         PFDR_HIP(hipStreamSynchronize(s));
         st.sums += since(t);
+        dCv.alloc(V);
+        dVc.alloc(V);
+        drVc.alloc((size_t)V + 1);
+        CPB_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+    }
+
+    // R = Y - A X at the graph's components and drX (:866-878): the component
+    // column sums of pfdr_cp_reduce, then k_cpb_residual, as the loop does
+    void residual_from_state() {
+        CPB_ABI(pfdr_cpgraph_get_components(g, nullptr, nullptr, dVc.p, drVc.p, PFDR_MEM_DEVICE));
+        DevBuf<real> rA((size_t)N * rV), L(rV);
+        if (sizeof(real) == 4)
+            CPB_ABI(pfdr_cp_reduce_f32(N, V, (const float *)pA, (const float *)dY.p, rV, drVc.p,
+                                       dVc.p, 0, PFDR_MEM_DEVICE, 1e-3f, 100, 10, (float *)rA.p,
+                                       nullptr, nullptr, (float *)L.p, nullptr));
+        else
+            CPB_ABI(pfdr_cp_reduce_f64(N, V, (const double *)pA, (const double *)dY.p, rV, drVc.p,
+                                       dVc.p, 0, PFDR_MEM_DEVICE, 1e-3, 100, 10, (double *)rA.p,
+                                       nullptr, nullptr, (double *)L.p, nullptr));
+        k_cpb_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rV, rA.p, drX.p, dY.p, dR.p);
+        PFDR_HIP(hipGetLastError());
+        PFDR_HIP(hipStreamSynchronize(s));
+    }
+
+    void adopt(int rV_new, const void *x, const void *R) override {
+        rV = rV_new;
+        drX.alloc(rV);
+        PFDR_HIP(hipMemcpyAsync(drX.p, x, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+        CPB_ABI(pfdr_cpgraph_set_values(g, drX.p, PFDR_MEM_DEVICE));
+        CPB_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+        if (N > 0) {
+            if (R) {
+                PFDR_HIP(hipMemcpyAsync(dR.p, R, sizeof(real) * N, hipMemcpyDeviceToDevice, s));
+                PFDR_HIP(hipStreamSynchronize(s));
+            } else {
+                residual_from_state();
+            }
+        }
+        obj_known = false;
+    }
+    const void *values() const override { return drX.p; }
+    const void *residual() const override { return N > 0 ? dR.p : nullptr; }
+    void forget_objective() override { obj_known = false; }
+    void stats(double *seconds, int64_t *counts) const override {
+        if (seconds) {
+            const double v[6] = {st.gradient, st.cuts, st.graph, st.pfdr, st.sums, st.total};
+            for (int i = 0; i < 6; i++) seconds[i] = v[i];
+        }
+        if (counts) {
+            counts[0] = st.ncuts;
+            counts[1] = st.rounds;
+            counts[2] = st.relabels;
+            counts[3] = st.pfdr_it;
+        }
+    }
+
+    void loop(clock::time_point t0, const pfdr_cp_params &q, int *CP_it_out, double *Time,
+              void *Obj_, void *Dif_) override {
+        const real CP_difTol = (real)q.CP_difTol, rho = (real)q.rho, condMin = (real)q.condMin,
+                   difRcd = (real)q.difRcd, difTol = (real)q.difTol;
+        const int CP_itMax = q.CP_itMax, itMax = q.itMax, verbose = q.verbose;
+        real *Obj = (real *)Obj_, *Dif = (real *)Dif_;
+        const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
+        const real eps = (real(0) < CP_difTol && CP_difTol < Lim<real>::eps) ? CP_difTol
+                                                                            : Lim<real>::eps;
+        const real inf = Lim<real>::huge;
+        const int gV = grid_for(V);
+        auto t = t0;
+        st = Stats{};
+        int rE = 0;  // a restart reports no reduced edge before its first iteration
+        if (Obj) Obj[0] = obj_known ? obj : std::numeric_limits<real>::quiet_NaN();
 
         // ---- cut pursuit
-        DevBuf<int> dCv(V), dVc(V), drVc((size_t)V + 1), dCv_;
+        DevBuf<int> dCv_;
         DevBuf<real> drX_, dtr(V), drc(E > 0 ? E : 1), t1, t2;
         DevBuf<uint8_t> dseg(V);
-        CPB_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
         const bool track = CP_difTol > real(0) || Dif;
         if (track) {
-            drX_.alloc(1);
+            drX_.alloc(rV);
             dCv_.alloc(V);
             t1.alloc(V);
             t2.alloc(V);
-            PFDR_HIP(hipMemcpyAsync(drX_.p, drX.p, sizeof(real), hipMemcpyDeviceToDevice, s));
+            PFDR_HIP(hipMemcpyAsync(drX_.p, drX.p, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
             PFDR_HIP(hipMemcpyAsync(dCv_.p, dCv.p, sizeof(int) * V, hipMemcpyDeviceToDevice, s));
             PFDR_HIP(hipStreamSynchronize(s));
         }
@@ -395,7 +463,7 @@ struct BdDriver {
                 CPB_ABI(pfdr_session_sync(ses));
                 st.pfdr_it += pit;
                 const void *x = pfdr_session_device_x(ses);
-                if (!x) throw AbiFail{PFDR_ERR_STATE};
+                if (!x) throw CpAbiFail{PFDR_ERR_STATE};
                 PFDR_HIP(hipMemcpyAsync(drX.p, x, sizeof(real) * rV, hipMemcpyDeviceToDevice, s));
                 PFDR_HIP(hipStreamSynchronize(s));
             }
@@ -444,18 +512,22 @@ struct BdDriver {
                     a = seq_sum(tt.p, rE);
                 }
                 Obj[it] += a;
+                obj = Obj[it];
             }
+            obj_known = Obj != nullptr;
             PFDR_HIP(hipStreamSynchronize(s));  // the iteration's buffers leave scope
             st.sums += since(t);
         }
-        // ---- the result
-        *rV_out = rV;
         if (CP_it_out) *CP_it_out = it;
+        st.total = since(t0);
+    }
+
+    void download(int *rV_out, int *Cv, void *rX_out) override {
+        *rV_out = rV;
         HostPins hp(s);
         hp.copy(Cv, dCv.p, sizeof(int) * V, hipMemcpyDeviceToHost);
         hp.copy(rX_out, drX.p, sizeof(real) * rV, hipMemcpyDeviceToHost);
         hp.release();
-        st.total = since(t0);
     }
 };
 
@@ -471,10 +543,27 @@ int cpb_entry(const char *fn, int V, int E, int N, int *rV, int *Cv, real *rX, c
     if (N < 0 && -N != V) return report_error(fn, "N < 0 needs A = A^tA and N = -V");
     if (!(min <= max)) return report_error(fn, "the bounds need min <= max");
     try {
+        const auto t0 = std::chrono::steady_clock::now();
+        g_stats = Stats{};
         BdDriver<real> d;
-        d.run(V, E, N, rV, Cv, rX, Y, A, Eu, Ev, La_d1, min, max, CP_difTol, CP_itMax, CP_it, rho,
-              condMin, difRcd, difTol, itMax, Time, Obj, Dif, verbose);
-    } catch (const AbiFail &f) {
+        struct Keep {  // what the call spent, also when it fails half way
+            BdDriver<real> &d;
+            ~Keep() { g_stats = d.st; }
+        } keep{d};
+        pfdr_cp_problem p{};
+        p.kind = PFDR_KIND_BOUNDS;
+        p.mem = PFDR_MEM_HOST;
+        p.V = V, p.E = E, p.N = N;
+        p.Y = Y, p.A = A, p.Eu = Eu, p.Ev = Ev, p.La_d1 = La_d1;
+        p.min = min, p.max = max;
+        const pfdr_cp_params q{CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose};
+        d.setup(p, Obj != nullptr);
+        const double init_sums = d.st.sums;
+        d.loop(t0, q, CP_it, Time, Obj, Dif);
+        d.download(rV, Cv, rX);
+        d.st.sums += init_sums;
+        d.st.total = BdDriver<real>::since(t0);
+    } catch (const CpAbiFail &f) {
         return f.status;
     } catch (const HipError &h) {
         return report_error(fn, h);
@@ -485,6 +574,11 @@ int cpb_entry(const char *fn, int V, int E, int N, int *rV, int *Cv, real *rX, c
 }
 
 }  // namespace
+
+CpDriverBase *cp_make_bounds_driver(int dtype) {
+    if (dtype == PFDR_F32) return new BdDriver<float>();
+    return new BdDriver<double>();
+}
 
 }  // namespace pfdr
 

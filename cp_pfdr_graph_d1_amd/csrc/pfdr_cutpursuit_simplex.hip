@@ -14,25 +14,24 @@
 // functional at the one-component solution (the reference's initialize()
 // :119-146 does not evaluate it for al != 0), and al outside [0, 1] is an
 // argument error (the reference's KL branch then reads constants it never set).
+//
+// The driver runs in three phases (pfdr_cp_driver.hpp): setup (upload, graph,
+// the reference's initialize()), the loop from the state the driver holds, and
+// the download.  An entry is the three in a row; the resumable solver
+// (pfdr_cp_solver.hip) keeps the driver and runs the same loop again.
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <stdexcept>
 #include <vector>
 
-#include "pfdr_graph.hpp"
+#include "pfdr_cp_driver.hpp"
 
 namespace pfdr {
 
 namespace {
 
-struct AbiFail {  // a library call failed: its message is already recorded
-    int status;
-};
-#define CPS_ABI(call)                              \
-    do {                                           \
-        const int st_ = (call);                    \
-        if (st_ != PFDR_OK) throw AbiFail{st_};    \
-    } while (0)
+#define CPS_ABI(call) CP_ABI(call)
 
 // What the last call on this thread spent where (pfdr_cp_loss_d1_simplex_stats).
 constexpr int kStatExp = 64;  // expansions whose rounds / relabels are kept one by one
@@ -156,11 +155,18 @@ void debug_log(long n, const real *x, real *out) {
 }
 
 template <typename real>
-struct SxDriver {
-    using clock = std::chrono::steady_clock;
-    hipStream_t s = lib_stream();
+struct SxDriver : CpDriverBase {
+    Stats st;  // of the last run
     DevBuf<int> off{2};
     DevBuf<real> one{1};
+    // the resident problem
+    DevBuf<real> dQ;
+    real al = real(0);
+    // the state besides the graph's: label vectors, reduced observations, Cv
+    DevBuf<real> drP, drQ;
+    DevBuf<int> dCv;
+    real obj = real(0);  // the functional at the state, when known
+    bool obj_known = false;
 
     // ((0 + x[0]) + x[1]) + ... in real
     real seq_sum(const real *x, long n) {
@@ -217,12 +223,73 @@ struct SxDriver {
         return a + b;
     }
 
-    void run(int K, int V, int E, real al, int *rV_out, int *Cv, real *rP_out, const real *Q,
-             const int *Eu, const int *Ev, const real *La_d1, real CP_difTol, int CP_itMax,
-             int *CP_it_out, real rho, real condMin, real difRcd, real difTol, int itMax,
-             double *Time, real *Obj, real *Dif, int verbose) {
-        const auto t0 = clock::now();
-        Stats &st = g_stats;
+    void setup(const pfdr_cp_problem &p, bool want_obj) override {
+        V = p.V, E = p.E, K = p.K;
+        al = (real)p.al;
+        const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
+        const long VK = (long)V * K;
+        // ---- the problem, once, into HBM
+        DevBuf<real> dLa;
+        DevBuf<int> dEu, dEv;
+        {
+            HostPins hp(s);
+            cp_take(dQ, (const real *)p.Y, (size_t)VK, p.mem, hp, s);
+            cp_take(dEu, p.Eu, (size_t)E, p.mem, hp, s);
+            cp_take(dEv, p.Ev, (size_t)E, p.mem, hp, s);
+            cp_take(dLa, (const real *)p.La_d1, (size_t)E, p.mem, hp, s);
+            hp.release();
+        }
+        CPS_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, nullptr, PFDR_MEM_DEVICE));
+        CPS_ABI(pfdr_cpgraph_simplex_setup(g, K, (double)al, dQ.p, PFDR_MEM_DEVICE));
+
+        // ---- initialize (:96-116): one component, its rP from the observations
+        rV = 1;
+        drP.alloc((size_t)K);
+        drQ.alloc((size_t)K);
+        CPS_ABI(pfdr_cpgraph_simplex_observations(g, drP.p, drQ.p, nullptr, PFDR_MEM_DEVICE));
+        dCv.alloc(V);
+        CPS_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+        // the functional itself, as every later Obj[k] with rV = 1
+        obj_known = false;
+        if (want_obj) {
+            const auto t = clock::now();
+            obj = objective(K, V, al, 1, 0, dCv.p, drP.p, drQ.p, dQ.p, nullptr, nullptr, nullptr);
+            obj_known = true;
+            st.sums += since(t);
+        }
+    }
+
+    void adopt(int rV_new, const void *x, const void *) override {
+        rV = rV_new;
+        drP.alloc((size_t)rV * K);
+        PFDR_HIP(hipMemcpyAsync(drP.p, x, sizeof(real) * rV * K, hipMemcpyDeviceToDevice, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+        CPS_ABI(pfdr_cpgraph_simplex_set_values(g, drP.p, PFDR_MEM_DEVICE));
+        CPS_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+        obj_known = false;
+    }
+    const void *values() const override { return drP.p; }
+    const void *residual() const override { return nullptr; }
+    void forget_objective() override { obj_known = false; }
+    void stats(double *seconds, int64_t *counts) const override {
+        if (seconds) {
+            const double v[6] = {st.gradient, st.cuts, st.graph, st.pfdr, st.sums, st.total};
+            for (int i = 0; i < 6; i++) seconds[i] = v[i];
+        }
+        if (counts) {
+            counts[0] = st.expansions;
+            counts[1] = st.rounds;
+            counts[2] = st.relabels;
+            counts[3] = st.pfdr_it;
+        }
+    }
+
+    void loop(clock::time_point t0, const pfdr_cp_params &q, int *CP_it_out, double *Time,
+              void *Obj_, void *Dif_) override {
+        const real CP_difTol = (real)q.CP_difTol, rho = (real)q.rho, condMin = (real)q.condMin,
+                   difRcd = (real)q.difRcd, difTol = (real)q.difTol;
+        const int CP_itMax = q.CP_itMax, itMax = q.itMax, verbose = q.verbose;
+        real *Obj = (real *)Obj_, *Dif = (real *)Dif_;
         st = Stats{};
         const int dt = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
         // :214-231 as compiled: (ZERO < c < a) is ((0 < c) < a), 1 < a never holds
@@ -235,55 +302,26 @@ struct SxDriver {
             eps = ((real)(real(0) < c) < a) ? c : a;
         }
         const long VK = (long)V * K;
-        // ---- the problem, once, into HBM
-        DevBuf<real> dQ, dLa;
-        DevBuf<int> dEu, dEv;
-        {
-            HostPins hp(s);
-            up(dQ, Q, (size_t)VK, hp);
-            up(dEu, Eu, (size_t)E, hp);
-            up(dEv, Ev, (size_t)E, hp);
-            up(dLa, La_d1, (size_t)E, hp);
-            hp.release();
-        }
-        pfdr_cpgraph *g = nullptr;
-        CPS_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, nullptr, PFDR_MEM_DEVICE));
-        struct Hold {
-            pfdr_cpgraph *g;
-            ~Hold() { pfdr_cpgraph_destroy(g); }
-        } hold{g};
-        CPS_ABI(pfdr_cpgraph_simplex_setup(g, K, (double)al, dQ.p, PFDR_MEM_DEVICE));
-
-        // ---- initialize (:96-116): one component, its rP from the observations
-        int rV = 1, rE = 0;
-        DevBuf<real> drP((size_t)K), drQ((size_t)K), drLaf(1);
-        CPS_ABI(pfdr_cpgraph_simplex_observations(g, drP.p, drQ.p, nullptr, PFDR_MEM_DEVICE));
-        DevBuf<int> dCv(V), dCv_, dlab, dlab_;
-        DevBuf<real> drP_, dtr(V), drc(E > 0 ? E : 1), tt;
+        int rE = 0;  // a restart reports no reduced edge before its first iteration
+        if (Obj) Obj[0] = obj_known ? obj : std::numeric_limits<real>::quiet_NaN();
+        DevBuf<int> dCv_, dlab, dlab_;
+        DevBuf<real> drP_, drLaf(1), dtr(V), drc(E > 0 ? E : 1), tt;
         DevBuf<uint8_t> dseg(V);
-        CPS_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
-        // Obj[0]: the functional itself, as every later Obj[k] with rV = 1
-        if (Obj) {
-            const auto t = clock::now();
-            Obj[0] = objective(K, V, al, 1, 0, dCv.p, drP.p, drQ.p, dQ.p, nullptr, nullptr,
-                               nullptr);
-            st.sums += since(t);
-        }
         // ---- tracking (:282-306)
         const bool track = CP_difTol > real(0) || Dif;
         const bool labels = CP_difTol >= real(1);
         if (track) {
             if (labels) {
-                dlab.alloc(1);
-                dlab_.alloc(1);
-                k_cps_labels<real><<<1, kBlock, 0, s>>>(1, K, drP.p, dlab_.p);
+                dlab.alloc(rV);
+                dlab_.alloc(rV);
+                k_cps_labels<real><<<grid_for(rV), kBlock, 0, s>>>(rV, K, drP.p, dlab_.p);
                 PFDR_HIP(hipGetLastError());
                 tt.alloc(V);
             } else {
                 if (VK >= (1L << 31)) throw std::runtime_error("sum of 2^31 or more terms");
-                drP_.alloc((size_t)K);
-                PFDR_HIP(hipMemcpyAsync(drP_.p, drP.p, sizeof(real) * K, hipMemcpyDeviceToDevice,
-                                        s));
+                drP_.alloc((size_t)rV * K);
+                PFDR_HIP(hipMemcpyAsync(drP_.p, drP.p, sizeof(real) * rV * K,
+                                        hipMemcpyDeviceToDevice, s));
                 tt.alloc((size_t)VK);
             }
             dCv_.alloc(V);
@@ -393,7 +431,7 @@ struct SxDriver {
                 CPS_ABI(pfdr_session_sync(ses));
                 st.pfdr_it += pit;
                 const void *x = pfdr_session_device_x(ses);
-                if (!x) throw AbiFail{PFDR_ERR_STATE};
+                if (!x) throw CpAbiFail{PFDR_ERR_STATE};
                 PFDR_HIP(hipMemcpyAsync(drP.p, x, sizeof(real) * rVK, hipMemcpyDeviceToDevice, s));
                 PFDR_HIP(hipStreamSynchronize(s));
             }
@@ -433,19 +471,22 @@ struct SxDriver {
             }
             it++;
             if (Obj)  // :870-917
-                Obj[it] = objective(K, V, al, rV, rE, dCv.p, drP.p, drQ.p, dQ.p, rEu.p, rEv.p,
-                                    rLa.p);
+                obj = Obj[it] = objective(K, V, al, rV, rE, dCv.p, drP.p, drQ.p, dQ.p, rEu.p,
+                                          rEv.p, rLa.p);
+            obj_known = Obj != nullptr;
             PFDR_HIP(hipStreamSynchronize(s));
             st.sums += since(t);
         }
-        // ---- the result
-        *rV_out = rV;
         if (CP_it_out) *CP_it_out = it;
+        st.total = since(t0);
+    }
+
+    void download(int *rV_out, int *Cv, void *rP_out) override {
+        *rV_out = rV;
         HostPins hp(s);
         hp.copy(Cv, dCv.p, sizeof(int) * V, hipMemcpyDeviceToHost);
         hp.copy(rP_out, drP.p, sizeof(real) * rV * K, hipMemcpyDeviceToHost);
         hp.release();
-        st.total = since(t0);
     }
 };
 
@@ -459,10 +500,27 @@ int cps_entry(const char *fn, int K, int V, int E, real al, int *rV, int *Cv, re
         return report_error(fn, "invalid arguments");
     if (!(al >= real(0) && al <= real(1))) return report_error(fn, "al must lie in [0, 1]");
     try {
+        const auto t0 = std::chrono::steady_clock::now();
+        g_stats = Stats{};
         SxDriver<real> d;
-        d.run(K, V, E, al, rV, Cv, rP, Q, Eu, Ev, La_d1, CP_difTol, CP_itMax, CP_it, rho, condMin,
-              difRcd, difTol, itMax, Time, Obj, Dif, verbose);
-    } catch (const AbiFail &f) {
+        struct Keep {  // what the call spent, also when it fails half way
+            SxDriver<real> &d;
+            ~Keep() { g_stats = d.st; }
+        } keep{d};
+        pfdr_cp_problem p{};
+        p.kind = PFDR_KIND_SIMPLEX;
+        p.mem = PFDR_MEM_HOST;
+        p.V = V, p.E = E, p.K = K;
+        p.Y = Q, p.Eu = Eu, p.Ev = Ev, p.La_d1 = La_d1;
+        p.al = al;
+        const pfdr_cp_params q{CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose};
+        d.setup(p, Obj != nullptr);
+        const double init_sums = d.st.sums;
+        d.loop(t0, q, CP_it, Time, Obj, Dif);
+        d.download(rV, Cv, rP);
+        d.st.sums += init_sums;
+        d.st.total = SxDriver<real>::since(t0);
+    } catch (const CpAbiFail &f) {
         return f.status;
     } catch (const HipError &h) {
         return report_error(fn, h);
@@ -473,6 +531,11 @@ int cps_entry(const char *fn, int K, int V, int E, real al, int *rV, int *Cv, re
 }
 
 }  // namespace
+
+CpDriverBase *cp_make_simplex_driver(int dtype) {
+    if (dtype == PFDR_F32) return new SxDriver<float>();
+    return new SxDriver<double>();
+}
 
 }  // namespace pfdr
 

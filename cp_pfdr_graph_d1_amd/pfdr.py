@@ -65,6 +65,10 @@ EXPORTED = (
     "pfdr_cp_loss_d1_simplex_stats",
     "pfdr_cp_quadratic_d1_bounds_f32", "pfdr_cp_quadratic_d1_bounds_f64",
     "pfdr_cp_quadratic_d1_bounds_stats",
+    "pfdr_cp_solver_create", "pfdr_cp_solver_destroy", "pfdr_cp_solver_run",
+    "pfdr_cp_solver_get_state", "pfdr_cp_solver_set_state", "pfdr_cp_solver_set_partition",
+    "pfdr_cp_solver_set_penalties", "pfdr_cp_solver_stats",
+    "pfdr_cpgraph_set_weights", "pfdr_cpgraph_set_active_by_labels",
     "pfdr_session_create", "pfdr_session_run", "pfdr_session_prepare", "pfdr_session_result",
     "pfdr_session_device_x", "pfdr_session_set_profiling", "pfdr_session_profile_filter",
     "pfdr_session_kernel_stats", "pfdr_session_sync",
@@ -112,7 +116,40 @@ class Problem(C.Structure):
     ]
 
 
+class CPProblem(C.Structure):
+    """Mirror of ``pfdr_cp_problem`` (include/pfdr_mi355x.h)."""
+    _fields_ = [
+        ("kind", C.c_int), ("duplex", C.c_int), ("dtype", C.c_int), ("mem", C.c_int),
+        ("V", C.c_int), ("E", C.c_int), ("N", C.c_int), ("K", C.c_int),
+        ("Y", C.c_void_p), ("A", C.c_void_p), ("Eu", C.c_void_p), ("Ev", C.c_void_p),
+        ("La_d1", C.c_void_p), ("La_l1", C.c_void_p),
+        ("positivity", C.c_int), ("min", C.c_double), ("max", C.c_double), ("al", C.c_double),
+    ]
+
+
+class CPParams(C.Structure):
+    """Mirror of ``pfdr_cp_params`` (include/pfdr_mi355x.h)."""
+    _fields_ = [
+        ("CP_difTol", C.c_double), ("CP_itMax", C.c_int),
+        ("rho", C.c_double), ("condMin", C.c_double), ("difRcd", C.c_double),
+        ("difTol", C.c_double), ("itMax", C.c_int), ("verbose", C.c_int),
+    ]
+
+
 _LIB = None
+
+
+def _solver_argtypes(lib, vp):
+    """the resumable solver takes its pointers as integers or ctypes pointers"""
+    lib.pfdr_cp_solver_create.argtypes = [C.POINTER(vp), C.POINTER(CPProblem)]
+    lib.pfdr_cp_solver_destroy.argtypes = [vp]
+    lib.pfdr_cp_solver_destroy.restype = None
+    lib.pfdr_cp_solver_run.argtypes = [vp, C.POINTER(CPParams), vp, vp, vp, vp]
+    lib.pfdr_cp_solver_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.pfdr_cp_solver_set_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]
+    lib.pfdr_cp_solver_set_partition.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    lib.pfdr_cp_solver_set_penalties.argtypes = [vp, vp, vp, C.c_int]
+    lib.pfdr_cp_solver_stats.argtypes = [vp, vp, vp, vp]
 
 
 def load():
@@ -151,6 +188,9 @@ def load():
         lib.pfdr_comm_init.argtypes = [C.POINTER(C.c_void_p), C.c_int,
                                        C.c_int, C.c_void_p]
         lib.pfdr_comm_destroy.argtypes = [C.c_void_p]
+        vp = C.c_void_p
+        if hasattr(lib, "pfdr_cp_solver_create"):  # (absent from an older PFDR_LIB_PATH build)
+            _solver_argtypes(lib, vp)
         # (PFDR_LIB_PATH: an A/B against a build of the previous ABI, 3, which
         # reads the problem without its trailing `spec` field)
         old_ok = bool(os.environ.get("PFDR_LIB_PATH")) and lib.pfdr_abi_version() == 3
@@ -328,6 +368,45 @@ class Lib:
                "pfdr_cp_loss_d1_simplex_" + sfx)
         return (Cv, rP[:rV.value * K].copy(), it.value, Obj,
                 None if Dif is None else Dif[:CP_itMax], Time)
+
+    # the resumable solver (pfdr_cp_solver_*): thin mirrors, pointers as integers
+    # or ctypes pointers; CPSolver below is the array-level face
+    def cp_solver_create(self, problem):
+        """pfdr_cp_solver_create(CPProblem) -> handle"""
+        h = C.c_void_p()
+        _check(self.lib.pfdr_cp_solver_create(C.byref(h), C.byref(problem)),
+               "pfdr_cp_solver_create")
+        return h
+
+    def cp_solver_destroy(self, handle):
+        self.lib.pfdr_cp_solver_destroy(handle)
+
+    def cp_solver_run(self, handle, params, CP_it=None, Time=None, Obj=None, Dif=None):
+        """pfdr_cp_solver_run(handle, CPParams, host pointers or None)"""
+        _check(self.lib.pfdr_cp_solver_run(handle, C.byref(params), CP_it, Time, Obj, Dif),
+               "pfdr_cp_solver_run")
+
+    def cp_solver_get_state(self, handle, rV=None, Cv=None, Vc=None, rVc=None, active=None,
+                            rX=None, R=None, mem=PFDR_MEM_HOST):
+        _check(self.lib.pfdr_cp_solver_get_state(handle, rV, Cv, Vc, rVc, active, rX, R, mem),
+               "pfdr_cp_solver_get_state")
+
+    def cp_solver_set_state(self, handle, rV, Cv, Vc, rVc, active, rX, R=None,
+                            mem=PFDR_MEM_HOST):
+        _check(self.lib.pfdr_cp_solver_set_state(handle, rV, Cv, Vc, rVc, active, rX, R, mem),
+               "pfdr_cp_solver_set_state")
+
+    def cp_solver_set_partition(self, handle, nlabels, label, values, mem=PFDR_MEM_HOST):
+        _check(self.lib.pfdr_cp_solver_set_partition(handle, nlabels, label, values, mem),
+               "pfdr_cp_solver_set_partition")
+
+    def cp_solver_set_penalties(self, handle, La_d1=None, La_l1=None, mem=PFDR_MEM_HOST):
+        _check(self.lib.pfdr_cp_solver_set_penalties(handle, La_d1, La_l1, mem),
+               "pfdr_cp_solver_set_penalties")
+
+    def cp_solver_stats(self, handle, seconds=None, counts=None, setup_seconds=None):
+        _check(self.lib.pfdr_cp_solver_stats(handle, seconds, counts, setup_seconds),
+               "pfdr_cp_solver_stats")
 
     def cp_loss_d1_simplex_stats(self, n_exp=64):
         """pfdr_cp_loss_d1_simplex_stats of this thread's last cp_loss_d1_simplex
@@ -1336,6 +1415,196 @@ class CPGraph:
         if self.h:
             load().pfdr_cpgraph_destroy(self.h)
             self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _is_device(a):
+    return hasattr(a, "data_ptr")
+
+
+class CPSolver:
+    """The resumable cut pursuit (pfdr_cp_solver_*): the problem, its graph and
+    the cut-pursuit state stay on the device between calls.
+
+    kind: "l1", "bounds" or "simplex" (or PFDR_KIND_*); duplex=True with "l1" is
+    the duplex driver.  Y_or_Q, A, N as the one-call entries (Q[V*K] vertex-major
+    with K for the simplex).  Every array is a numpy array (host) or a torch
+    tensor on the GPU (device pointers; copied by the library, except A, which
+    is borrowed and kept alive here).  The first run() equals the matching
+    Lib.cp_* call byte for byte; every later one is the reference's warm restart
+    from the state the handle holds."""
+
+    KINDS = {"l1": PFDR_KIND_L1, "bounds": PFDR_KIND_BOUNDS, "simplex": PFDR_KIND_SIMPLEX}
+
+    def __init__(self, kind, Y_or_Q, Eu, Ev, La_d1, A=None, N=0, La_l1=None, positivity=0,
+                 lo=-np.inf, hi=np.inf, K=0, al=0.1, duplex=False):
+        self._L = Lib()
+        self.kind = self.KINDS.get(kind, kind)
+        self._h = None
+        dev = _is_device(Y_or_Q)
+        if dev:
+            import torch
+            self.dtype = np.dtype(str(Y_or_Q.dtype).replace("torch.", ""))
+            _producers_done()
+            size = lambda a: int(a.numel())
+            ints = lambda a: a.to(torch.int32).contiguous()
+            reals = lambda a: a.contiguous()
+        else:
+            Y_or_Q = np.ascontiguousarray(Y_or_Q)
+            self.dtype = Y_or_Q.dtype
+            size = lambda a: int(a.size)
+            ints = lambda a: np.ascontiguousarray(a, np.int32)
+            reals = lambda a: np.ascontiguousarray(a, self.dtype).ravel()
+        self._ct, _, dcode = _real(self.dtype)
+        self.device = dev
+        simplex = self.kind == PFDR_KIND_SIMPLEX
+        self.K = int(K) if simplex else 1
+        self.N = 0 if simplex else int(N)
+        arrs = [None if a is None else reals(a) for a in (Y_or_Q, A, La_d1, La_l1)]
+        Eu, Ev = ints(Eu), ints(Ev)
+        if self.N > 0 and arrs[1] is not None:
+            self.V = size(arrs[1]) // self.N
+        else:
+            self.V = size(arrs[0]) // max(self.K, 1)
+        self.E = size(Eu)
+        self._keep = arrs + [Eu, Ev]  # A is borrowed for the solver's lifetime
+        p = CPProblem()
+        p.kind, p.duplex, p.dtype = self.kind, int(bool(duplex)), dcode
+        p.mem = PFDR_MEM_DEVICE if dev else PFDR_MEM_HOST
+        p.V, p.E, p.N, p.K = self.V, self.E, self.N, int(K) if simplex else 0
+        p.Y, p.A, p.La_d1, p.La_l1 = (self._addr(a) for a in arrs)
+        p.Eu, p.Ev = self._addr(Eu), self._addr(Ev)
+        p.positivity, p.min, p.max, p.al = int(positivity), lo, hi, al
+        self.has_l1 = La_l1 is not None
+        self._h = self._L.cp_solver_create(p)
+        if not dev:
+            self._keep = []
+
+    @staticmethod
+    def _addr(a):
+        if a is None:
+            return None
+        return a.data_ptr() if _is_device(a) else a.ctypes.data
+
+    def run(self, CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0, difTol=1e-4,
+            itMax=10000, verbose=0, obj=True, dif=True, time=True):
+        """-> (Cv[V] int32, rX[rV] (rP[rV*K]), CP_it, Obj[CP_itMax + 1], Dif[CP_itMax],
+        Time[CP_itMax + 1]); a record not asked for is passed as NULL and None"""
+        CP_itMax = int(CP_itMax)
+        q = CPParams(CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, int(itMax), int(verbose))
+        Obj = np.zeros(CP_itMax + 1, self.dtype) if obj else None
+        Dif = np.zeros(max(CP_itMax, 1), self.dtype) if dif else None
+        Time = np.zeros(CP_itMax + 1, np.float64) if time else None
+        it = C.c_int(0)
+        self._L.cp_solver_run(self._h, q, C.addressof(it), self._addr(Time), self._addr(Obj),
+                              self._addr(Dif))
+        Cv = np.zeros(self.V, np.int32)
+        rX = np.zeros(self.V * self.K, self.dtype)
+        rV = C.c_int(0)
+        self._L.cp_solver_get_state(self._h, rV=C.addressof(rV), Cv=Cv.ctypes.data,
+                                    rX=rX.ctypes.data)
+        return (Cv, rX[:rV.value * self.K].copy(), it.value, Obj,
+                None if Dif is None else Dif[:CP_itMax], Time)
+
+    def state(self, device=False):
+        """-> dict: active[E] uint8, Cv[V], Vc[V], rVc[rV + 1] int32, rX[rV]
+        (rP[rV*K]) and, for N > 0, R[N]; numpy arrays, or torch tensors on the GPU"""
+        V, E, K = self.V, self.E, self.K
+        rV = C.c_int(0)
+        if device:
+            import torch
+            td = getattr(torch, self.dtype.name)
+            new = lambda n, t: torch.empty(max(n, 1), dtype=t, device="cuda")
+            i32, u8 = torch.int32, torch.uint8
+        else:
+            td, i32, u8 = self.dtype, np.int32, np.uint8
+            new = lambda n, t: np.zeros(max(n, 1), t)
+        st = dict(active=new(E, u8), Cv=new(V, i32), Vc=new(V, i32), rVc=new(V + 1, i32),
+                  rX=new(V * K, td))
+        if self.N > 0:
+            st["R"] = new(self.N, td)
+        self._L.cp_solver_get_state(
+            self._h, C.addressof(rV), self._addr(st["Cv"]), self._addr(st["Vc"]),
+            self._addr(st["rVc"]), self._addr(st["active"]), self._addr(st["rX"]),
+            self._addr(st.get("R")), PFDR_MEM_DEVICE if device else PFDR_MEM_HOST)
+        r = rV.value
+        st["active"] = st["active"][:E]
+        st["rVc"] = st["rVc"][:r + 1]
+        st["rX"] = st["rX"][:r * K]
+        return st
+
+    def set_state(self, state, R="given"):
+        """Replace the state (a dict as state() returns; torch tensors on the GPU
+        are read in place).  R=None: the residual is recomputed on the device;
+        by default state["R"] is used when present."""
+        dev = _is_device(state["Cv"])
+        if dev:
+            _producers_done()
+            cvt = lambda a, t: a.contiguous()
+            rV = int(state["rVc"].numel()) - 1
+        else:
+            cvt = lambda a, t: np.ascontiguousarray(a, t)
+            rV = int(np.size(state["rVc"])) - 1
+        Cv, Vc, rVc = (cvt(state[k], np.int32) for k in ("Cv", "Vc", "rVc"))
+        act = cvt(state["active"], np.uint8)
+        rX = cvt(state["rX"], self.dtype)
+        Rv = state.get("R") if isinstance(R, str) else R
+        Rv = None if Rv is None or self.N <= 0 else cvt(Rv, self.dtype)
+        self._L.cp_solver_set_state(
+            self._h, rV, self._addr(Cv), self._addr(Vc), self._addr(rVc),
+            self._addr(act) if self.E > 0 else None, self._addr(rX), self._addr(Rv),
+            PFDR_MEM_DEVICE if dev else PFDR_MEM_HOST)
+
+    def set_partition(self, label, values):
+        """A state from a label per vertex and a value per label (what the
+        drivers return): edges between labels become active, the components are
+        those of that activity, each takes its label's value"""
+        dev = _is_device(label)
+        if dev:
+            _producers_done()
+            label, values = label.contiguous(), values.contiguous()
+            n = int(values.numel()) // self.K
+        else:
+            label = np.ascontiguousarray(label, np.int32)
+            values = np.ascontiguousarray(values, self.dtype).ravel()
+            n = values.size // self.K
+        self._L.cp_solver_set_partition(self._h, n, self._addr(label), self._addr(values),
+                                        PFDR_MEM_DEVICE if dev else PFDR_MEM_HOST)
+
+    def set_penalties(self, La_d1=None, La_l1=None):
+        """Overwrite La_d1[E] and / or La_l1[V]; the state is kept"""
+        dev = _is_device(La_d1) or _is_device(La_l1)
+        if dev:
+            _producers_done()
+            cvt = lambda a: None if a is None else a.contiguous()
+        else:
+            cvt = lambda a: None if a is None else np.ascontiguousarray(a, self.dtype).ravel()
+        La_d1, La_l1 = cvt(La_d1), cvt(La_l1)
+        self._L.cp_solver_set_penalties(self._h, self._addr(La_d1), self._addr(La_l1),
+                                        PFDR_MEM_DEVICE if dev else PFDR_MEM_HOST)
+
+    def stats(self):
+        """-> dict: seconds per phase and counts of the last run, and the seconds
+        the constructor's setup took"""
+        sec = np.zeros(6, np.float64)
+        cnt = np.zeros(4, np.int64)
+        setup = C.c_double(0)
+        self._L.cp_solver_stats(self._h, sec.ctypes.data, cnt.ctypes.data, C.addressof(setup))
+        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
+        out.update(zip(("n_cuts", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
+        out["setup"] = setup.value
+        return out
+
+    def close(self):
+        if self._h is not None:
+            self._L.cp_solver_destroy(self._h)
+            self._h = None
+            self._keep = []
 
     def __del__(self):
         try:

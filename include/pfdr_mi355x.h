@@ -477,8 +477,9 @@ int pfdr_cpgraph_simplex_labels(pfdr_cpgraph *g, int *Djv, int mem);
 
 /* -------------------------------------------------- whole cut pursuit -- */
 /* CP_PFDR_graph_quadratic_d1_l1<real> of the reference (arguments as
- * include/CP_PFDR_graph_quadratic_d1_l1.hpp:52-61, without the restart
- * record), the loop above with pfdr_cpgraph_mincut and the PFDR solver,
+ * include/CP_PFDR_graph_quadratic_d1_l1.hpp:52-61; the restart record is
+ * pfdr_cp_solver_* below), the loop above with pfdr_cpgraph_mincut and the
+ * PFDR solver,
  * everything resident on the current device: host arrays come in once, Cv[V]
  * and rX[*rV] (capacity V) go out once.  N > 0: A N-by-V column major, Y[N];
  * N = -V: A = A^tA, Y = A^tY; N = 0: A diagonal or NULL, Y = A^tY.  La_l1
@@ -497,8 +498,9 @@ int pfdr_cp_quadratic_d1_l1_f64(int V, int E, int N, int *rV, int *Cv, double *r
     double *Time, double *Obj, double *Dif, int verbose);
 
 /* CP_PFDR_graph_quadratic_d1_l1_duplex<real> of the reference (arguments as
- * include/CP_PFDR_graph_quadratic_d1_l1.hpp:133-142, without the restart
- * record): pfdr_cp_quadratic_d1_l1's loop with one two-layer cut per
+ * include/CP_PFDR_graph_quadratic_d1_l1.hpp:133-142; the restart record is
+ * pfdr_cp_solver_* below): pfdr_cp_quadratic_d1_l1's loop with one two-layer
+ * cut per
  * iteration in place of its two cuts -- gradient,
  * pfdr_cpgraph_capacities_duplex, pfdr_cpgraph_mincut_duplex,
  * pfdr_cpgraph_activate_duplex -- and everything else (initialisation, eps,
@@ -533,7 +535,8 @@ int pfdr_cp_quadratic_d1_l1_duplex_f64(int V, int E, int N, int *rV, int *Cv, do
 int pfdr_cp_quadratic_d1_l1_duplex_stats(double *seconds, int64_t *counts);
 
 /* CP_PFDR_graph_quadratic_d1_bounds<real> of the reference (arguments as
- * include/CP_PFDR_graph_quadratic_d1_bounds.hpp, without the restart record):
+ * include/CP_PFDR_graph_quadratic_d1_bounds.hpp; the restart record is
+ * pfdr_cp_solver_* below):
  * the same loop for the box min <= x <= max (+-HUGE_VAL: no bound) -- the
  * one-component least-squares value projected onto the box, one cut when
  * there is no bound and two otherwise (pfdr_cpgraph_capacities_bounds,
@@ -566,8 +569,9 @@ int pfdr_cp_quadratic_d1_bounds_f64(int V, int E, int N, int *rV, int *Cv, doubl
 int pfdr_cp_quadratic_d1_bounds_stats(double *seconds, int64_t *counts);
 
 /* CP_PFDR_graph_loss_d1_simplex<real> of the reference (arguments as
- * include/CP_PFDR_graph_loss_d1_simplex.hpp:41-48, without the restart
- * record): the simplex driver's loop above -- gradient, K - 1 alpha-expansions
+ * include/CP_PFDR_graph_loss_d1_simplex.hpp:41-48; the restart record is
+ * pfdr_cp_solver_* below): the simplex driver's loop above -- gradient, K - 1
+ * alpha-expansions
  * with pfdr_cpgraph_mincut (PFDR_ARCS_FORWARD), activation, components,
  * reduced graph, observations, the simplex PFDR solver from the components'
  * own optima, merge -- everything resident on the current device: host arrays
@@ -606,6 +610,98 @@ int pfdr_cp_loss_d1_simplex_f64(int K, int V, int E, double al, int *rV, int *Cv
  * the last one run or kept). */
 int pfdr_cp_loss_d1_simplex_stats(double *seconds, int64_t *counts, int64_t *exp_rounds,
     int64_t *exp_relabels, int n_exp);
+
+/* ------------------------------------------- resumable cut pursuit -- */
+/* The restart record of the reference's drivers (CP_restart, their last
+ * argument) as a handle: the problem, its pfdr_cpgraph and the cut-pursuit
+ * state stay on the device between calls.  create is the setup of the matching
+ * one-call entry (upload, graph, the reference's initialize()) and leaves the
+ * one-component state; the first run equals that entry byte for byte, Obj[0]
+ * included.  Every later run, and every run after set_state / set_partition /
+ * set_penalties, is the reference's warm restart
+ * (src/CP_PFDR_graph_quadratic_d1_l1.cpp:293-319): the iteration counter starts
+ * at 0, dif at max(CP_difTol^2, 1) (simplex: max(CP_difTol, 1)), the first
+ * preAt decision of N > 0 is taken with PFDR_itMax, the state is its own
+ * previous iterate, Time counts from the call.  So a resumed run iterates
+ * again even when the last one stopped on dif.  Obj[0] of a resumed run is the
+ * last Obj this handle computed (the reference leaves it unwritten); after
+ * set_state, set_partition, set_penalties, or a run without Obj, it is NaN. */
+typedef struct pfdr_cp_problem {
+    int kind;             /* PFDR_KIND_L1 / PFDR_KIND_BOUNDS / PFDR_KIND_SIMPLEX */
+    int duplex;           /* PFDR_KIND_L1 only: the duplex driver */
+    int dtype;            /* PFDR_F32 / PFDR_F64: type of every real array */
+    int mem;              /* PFDR_MEM_*: location of every array below.  Device
+                             arrays are copied, except A, which is borrowed: it
+                             must stay valid and unchanged until destroy */
+    int V, E, N, K;       /* as the entries (K only for the simplex, N not) */
+    const void *Y;        /* Y / A^tY, or Q[V*K] for the simplex */
+    const void *A;        /* as the entries; NULL for identity */
+    const int *Eu, *Ev;
+    const void *La_d1;    /* length E */
+    const void *La_l1;    /* length V or NULL (PFDR_KIND_L1 only) */
+    int positivity;       /* PFDR_KIND_L1 only */
+    double min, max;      /* PFDR_KIND_BOUNDS only (+-HUGE_VAL for none) */
+    double al;            /* simplex only */
+} pfdr_cp_problem;
+
+typedef struct pfdr_cp_params {
+    double CP_difTol;
+    int CP_itMax;
+    double rho, condMin, difRcd, difTol;
+    int itMax;
+    int verbose;
+} pfdr_cp_params;
+
+typedef struct pfdr_cp_solver pfdr_cp_solver;
+
+/* Argument errors are the matching entry's, before any device work. */
+int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem *p);
+void pfdr_cp_solver_destroy(pfdr_cp_solver *s);
+/* Host outputs, any may be NULL: Time[CP_itMax + 1], Obj[CP_itMax + 1],
+ * Dif[CP_itMax] of the solver's real type. */
+int pfdr_cp_solver_run(pfdr_cp_solver *s, const pfdr_cp_params *q, int *CP_it,
+                       double *Time, void *Obj, void *Dif);
+/* The state, any output may be NULL, host or device per mem: Cv[V], Vc[V],
+ * rVc[*rV + 1] (capacity V + 1), active[E], rX[*rV] (capacity V; simplex
+ * rP[*rV * K] vertex-major, capacity K V), R[N] = Y - A X (N > 0 only). */
+int pfdr_cp_solver_get_state(pfdr_cp_solver *s, int *rV, int *Cv, int *Vc, int *rVc,
+                             uint8_t *active, void *rX, void *R, int mem);
+/* Replaces the state after checking it on the device (only a flag word comes
+ * back): 1 <= rV <= V; rVc[0] = 0, rVc[rV] = V, strictly increasing; Vc a
+ * permutation of [0, V); Cv[Vc[i]] the component whose range holds i;
+ * active[e] 0 or 1; no NaN in rX or R; bounds: rX within [min, max].  A failed
+ * check is PFDR_ERR_ARG naming it, and the solver is left as it was.
+ * R = NULL (N > 0): recomputed in the reference's order (:889-901) by the
+ * loop's own kernels, pfdr_cp_reduce's component column sums without
+ * premultiplication and the loop's residual kernel: the bytes the loop holds
+ * after an iteration that worked on rA directly.  (After a premultiplied
+ * iteration the loop's R comes from column sums that were never scaled and
+ * scaled back by the equilibration, and may differ in the last bit.) */
+int pfdr_cp_solver_set_state(pfdr_cp_solver *s, int rV, const int *Cv, const int *Vc,
+                             const int *rVc, const uint8_t *active, const void *rX,
+                             const void *R, int mem);
+/* A state from what the drivers return: label[V] in [0, nlabels) and
+ * values[nlabels] (simplex nlabels K).  Edge e becomes active iff its ends'
+ * labels differ; the components are pfdr_cpgraph_components of that activity
+ * (a label class that is not connected becomes several); each takes the value
+ * of the label of the first vertex of its range; R is recomputed. */
+int pfdr_cp_solver_set_partition(pfdr_cp_solver *s, int nlabels, const int *label,
+                                 const void *values, int mem);
+/* Overwrites La_d1[E] and / or La_l1[V] (NULL: unchanged; La_l1 only if the
+ * solver was created with one); negative or NaN weights are PFDR_ERR_ARG.
+ * The state is kept and the next run is a restart. */
+int pfdr_cp_solver_set_penalties(pfdr_cp_solver *s, const void *La_d1,
+                                 const void *La_l1, int mem);
+/* seconds[6] / counts[4] of the last run in pfdr_cp_quadratic_d1_bounds_stats'
+ * layout (simplex: counts[0] = expansions), and the seconds create spent.
+ * Any may be NULL. */
+int pfdr_cp_solver_stats(pfdr_cp_solver *s, double *seconds, int64_t *counts,
+                         double *setup_seconds);
+/* La_d1[E] / La_l1[V] of a graph, in place (NULL: unchanged).  The graph
+ * caches topology only (incidence lists, the cut's CSRs), never weights. */
+int pfdr_cpgraph_set_weights(pfdr_cpgraph *g, const void *La_d1, const void *La_l1, int mem);
+/* active[e] = (label[Eu[e]] != label[Ev[e]]), label[V] any ints */
+int pfdr_cpgraph_set_active_by_labels(pfdr_cpgraph *g, const int *label, int mem);
 
 /* ------------------------------------------------------ multi-GPU comm -- */
 /* Partitioned sessions (quadratic solvers, identity or diagonal A): every
