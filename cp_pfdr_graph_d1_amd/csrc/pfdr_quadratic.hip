@@ -12,6 +12,7 @@
 #include "pfdr_order.hpp"
 #include "pfdr_quadratic_kernels.hpp"
 #include "pfdr_sort.hpp"
+#include "pfdr_sparse.hpp"
 
 namespace pfdr {
 
@@ -113,7 +114,7 @@ __global__ void k_remap_push(long n, long E, const unsigned *__restrict__ inv,
 template <typename real>
 class QuadSession final : public SessionBase {
   public:
-    explicit QuadSession(const pfdr_problem *p);
+    explicit QuadSession(const pfdr_problem *p, const pfdr_csc *csc = nullptr);
     ~QuadSession() override {
         if (hctrl_) {
             (void)hipStreamSynchronize(stream);  // no control-block copy in flight
@@ -388,6 +389,30 @@ class QuadSession final : public SessionBase {
     void plan_pad();
     PadOut<real> pad_out() const { return PadOut<real>{pad_ ? sl_.p : nullptr, wzp_.p}; }
     template <int EPI> void col_product(ColArgs<real> ca);
+    // sparse A (pfdr_sparse.hpp): the session runs as a direct-mode one
+    // (mode_ = A_DIRECT: Y of length N, R_, the objective's residual term, no
+    // tiny or fused path) whose four products walk the CSC / CSR instead of A_
+    bool sparse_ = false;
+    SparseOp<real> sp_;
+    // Sessions whose products run in the reference's order (exact_, or a
+    // sparse A on its sequential kernels; direct mode, weights >= 0) sum the
+    // recorded objective in that order too (k_obj_terms, three mono_sum's):
+    // Obj is then the reference's, bit for bit, like X, it and Dif.
+    // oterms_ = the terms of the N rows, E edges (caller's edge order: oemap_
+    // keeps a tiled session's edge positions) and V vertices, each part
+    // 16-byte aligned.
+    bool seqobj_ = false;
+    DevBuf<real> oterms_;
+    DevBuf<int> oemap_;
+    DevBuf<char> ows_;
+    long ot_e_ = 0, ot_v_ = 0;  // offsets of the edge and vertex terms
+  public:
+    bool sparse_csr(int64_t *rowptr, int32_t *colidx, void *rval) override {
+        if (!sparse_) return false;
+        sp_.read_csr(rowptr, colidx, rval, stream);
+        return true;
+    }
+  private:
     DevBuf<real> spart_;
     void plan_symv();
     template <int EPI> void ata_product(ColArgs<real> ca);
@@ -395,7 +420,7 @@ class QuadSession final : public SessionBase {
 
 // ----------------------------------------------------------------- setup --
 template <typename real>
-QuadSession<real>::QuadSession(const pfdr_problem *p) {
+QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
     if (p->V <= 0 || p->E < 0) throw std::runtime_error("V must be > 0 and E >= 0");
     if (!p->X || !p->Y || !p->Eu || !p->Ev || !p->La_d1)
         throw std::runtime_error("X, Y, Eu, Ev and La_d1 are required");
@@ -412,7 +437,18 @@ QuadSession<real>::QuadSession(const pfdr_problem *p) {
     if (N_ > 0) mode_ = A_DIRECT;
     else if (N_ < 0) mode_ = A_ATA;
     else mode_ = p->A ? A_DIAG : A_IDENT;
-    if (mode_ == A_DIRECT && !p->A) throw std::runtime_error("N > 0 requires A");
+    sparse_ = csc != nullptr;
+    if (sparse_) {
+        if (N_ <= 0) throw std::runtime_error("sparse A requires N > 0");
+        if (p->A) throw std::runtime_error("sparse A given together with a dense A");
+        if (p->nranks > 1 || p->comm)
+            throw std::runtime_error("sparse A is for one GPU (no partition, no communicator)");
+        if (!csc->colptr || !csc->rowidx || !csc->val)
+            throw std::runtime_error("sparse A: colptr, rowidx and val are required");
+        if (csc->nnz <= 0 || csc->nnz >= (1LL << 31) - 256)
+            throw std::runtime_error("sparse A: nnz must be in [1, 2^31 - 256)");
+    }
+    if (mode_ == A_DIRECT && !p->A && !sparse_) throw std::runtime_error("N > 0 requires A");
     if (mode_ == A_ATA && !p->A) throw std::runtime_error("N < 0 requires A = A^tA");
     rho_ = (real)p->rho;
     condMin_ = (real)p->condMin;
@@ -481,7 +517,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p) {
     if (mode_ == A_ATA && -(long)N_ != Vglob_)
         throw std::runtime_error("N < 0 requires A = A^tA (columns of the owned vertices, "
                                  "length V) and N = -V (V over all ranks)");
-    if ((mode_ == A_DIRECT || mode_ == A_ATA) && !halo_) {
+    if ((mode_ == A_DIRECT || mode_ == A_ATA) && !halo_ && !sparse_) {
         const long chain = mode_ == A_DIRECT ? std::max<long>(N_, V_) : (long)V_;
         exact_ = chain <= kExactChain;
         dense_exact = exact_ ? 1 : 0;
@@ -491,11 +527,23 @@ QuadSession<real>::QuadSession(const pfdr_problem *p) {
     copy_in(La_d1_, p->La_d1, E, mem, s, pins_);
     if (flavour_ == 0) copy_in(La_l1_, p->La_l1, V, mem, s, pins_);
     copy_in(Y_, p->Y, mode_ == A_DIRECT ? (size_t)N_ : V, mem, s, pins_);
-    const size_t asz = mode_ == A_DIRECT ? (size_t)N_ * V : mode_ == A_ATA ? (size_t)Vglob_ * V
-                     : mode_ == A_DIAG ? V : 0;
+    const size_t asz = sparse_ ? 0 : mode_ == A_DIRECT ? (size_t)N_ * V
+                     : mode_ == A_ATA ? (size_t)Vglob_ * V : mode_ == A_DIAG ? V : 0;
     copy_in(A_, p->A, asz, mem, s, pins_);
+    if (sparse_) {  // checked copy of the CSC, CSR view, kernel family
+        sp_.setup(V_, N_, csc, mem, kExactChain, s, pins_);
+        sparse_exact = sp_.exact ? 1 : 0;
+        sparse_nnz = sp_.nnz;
+        sparse_seg_col = sp_.gc;
+        sparse_seg_row = sp_.gr;
+        sparse_csr_us = (int64_t)(sp_.csr_ms * 1e3);
+    }
     if (emap_.p) {  // edge weights into the internal edge order
         permute(La_d1_, emap_.p, E, s);
+        if (sparse_ && rec_obj_) {  // (the objective's TV sum runs in the caller's edge order)
+            std::swap(oemap_.p, emap_.p);
+            std::swap(oemap_.n, emap_.n);
+        }
         emap_.release();
     }
     if (reordered_) {  // inputs into the internal labels (identity / diagonal A only)
@@ -555,7 +603,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p) {
         rows_nb_ = std::max(1, std::min(512, (V_ + 63) / 64));
         rows_cpb_ = (V_ + rows_nb_ - 1) / rows_nb_;
         rows_nb_ = (V_ + rows_cpb_ - 1) / rows_cpb_;
-        Rpart_.alloc((size_t)rows_nb_ * N_);
+        if (!sparse_) Rpart_.alloc((size_t)rows_nb_ * N_);
     }
     if (mode_ == A_ATA) { pre_.alloc(V); xout_.alloc(V); xfull_.alloc(Vglob_); plan_symv(); }
     if (mode_ == A_DIRECT && halo_) Rsum_.alloc(N_);
@@ -578,7 +626,20 @@ QuadSession<real>::QuadSession(const pfdr_problem *p) {
     if (mode_ == A_DIRECT) {
         ColArgs<real> ca{};
         ca.A = A_.p; ca.ncols = V_; ca.len = N_; ca.out = diag_.p;
-        col_product<EPI_SELF>(ca);
+        // (a sparse session's two setup products are always timed: profiling
+        // cannot be switched on before the session exists)
+        const bool pon = prof.on;
+        prof.on = pon || sparse_;
+        {
+            ProfScope ps(prof, "diag_cols", s);
+            col_product<EPI_SELF>(ca);
+        }
+        prof.on = pon;
+        if (sparse_) {
+            k_sp_norm_check<real><<<grid_for(V), kBlock, 0, s>>>(V_, diag_.p, sp_.word.p);
+            PFDR_HIP(hipGetLastError());
+            sp_throw(sp_.verdict(s));
+        }
     } else {
         k_diag<real><<<grid_for(V), kBlock, 0, s>>>(V_, mode_, A_.p, Vglob_, v0_, diag_.p);
     }
@@ -600,6 +661,23 @@ QuadSession<real>::QuadSession(const pfdr_problem *p) {
         grad_.release();
     } else {
         forward_dense(GATE_NONE);
+    }
+    if (rec_obj_ && mode_ == A_DIRECT && !halo_ && (exact_ || (sparse_ && sp_.exact))) {
+        DevBuf<int> neg(1);
+        PFDR_HIP(hipMemsetAsync(neg.p, 0, sizeof(int), s));
+        if (E_) k_negative_check<real><<<grid_for(E), kBlock, 0, s>>>(E_, La_d1_.p, neg.p);
+        if (La_l1_.p) k_negative_check<real><<<grid_for(V), kBlock, 0, s>>>(V_, La_l1_.p, neg.p);
+        PFDR_HIP(hipGetLastError());
+        int bad = 1;
+        PFDR_HIP(hipMemcpyAsync(&bad, neg.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+        seqobj_ = bad == 0;
+        if (seqobj_) {
+            ot_e_ = ((long)N_ + 3) / 4 * 4;
+            ot_v_ = ot_e_ + (E_ + 3) / 4 * 4;
+            oterms_.alloc((size_t)ot_v_ + V);
+            ows_.alloc(mono_ws_bytes<real>(std::max<long>(std::max<long>(N_, E_), V_)));
+        }
     }
     if (rec_obj_) objective();  // Obj[0]
     PFDR_HIP(hipStreamSynchronize(s));
@@ -647,6 +725,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p) {
                             &vpart_, &opart_, &Obj_, &Dif_, &xout_, &Rsum_, &xfull_, &spart_})
         acc(b->n * sizeof(real));
     acc(Rpart_.n * sizeof(double));
+    acc(sp_.bytes());
     acc((xp_.n + gi_.n) * sizeof(R2<real>) + inc_.ptr.n * 4 + inc_.idx.n * 4);
     acc((uptr_.n + mask_.n + oidx_.n + blkok_.n) * 4);
     acc(slots_.n * sizeof(Slots12) + luv_.n * 2 + deg8_.n +
@@ -1181,6 +1260,10 @@ template <typename real>
 void QuadSession<real>::gemv_rows(int gate) {
     hipStream_t s = stream;
     ProfScope ps(prof, "gemv_rows", s);
+    if (sparse_) {
+        sp_.rows(xp_.p, Y_.p, R_.p, gate ? ctrl_.p : nullptr, gate, s);
+        return;
+    }
     if (exact_) {
         k_rows_seq<real><<<grid_for(N_), kBlock, 0, s>>>(N_, V_, A_.p, xp_.p, Y_.p, R_.p,
                                                         gate ? ctrl_.p : nullptr, gate);
@@ -1269,6 +1352,7 @@ template <typename real>
 template <int EPI>
 void QuadSession<real>::col_product(ColArgs<real> ca) {
     hipStream_t s = stream;
+    if (sparse_) { sp_.template cols<EPI>(ca, s); return; }
     if (exact_)
         k_col_seq<real, EPI><<<grid_for(ca.ncols), kBlock, 0, s>>>(ca);
     else
@@ -1331,7 +1415,13 @@ void QuadSession<real>::amplitude(bool init) {
     if (init && mode_ == A_DIRECT) {
         ColArgs<real> ca{};
         ca.A = A_.p; ca.ncols = V_; ca.len = N_; ca.w = Y_.p; ca.out = pre_.p; ca.div = diag_.p;
-        col_product<EPI_DIV>(ca);
+        const bool pon = prof.on;
+        prof.on = pon || sparse_;  // (as the diagonal's product)
+        {
+            ProfScope ps(prof, "pinv_cols", s);
+            col_product<EPI_DIV>(ca);
+        }
+        prof.on = pon;
     }
     k_amp<real><<<nbv_, kBlock, 0, s>>>(V_, init ? (mode_ == A_DIRECT ? 1 : 0) : 2, Y_.p, diag_.p,
                                         pre_.p, xp_.p, absval_.p, cnt_part_.p);
@@ -1428,6 +1518,23 @@ template <typename real>
 void QuadSession<real>::objective() {
     hipStream_t s = stream;
     const Ctrl<real> *c = ctrl_.p;
+    if (seqobj_) {  // the three sums term by term, as the reference adds them
+        real *tn = oterms_.p, *te = oterms_.p + ot_e_, *tv = oterms_.p + ot_v_;
+        const long nmax = std::max<long>(std::max<long>(N_, E_), V_);
+        k_obj_terms<real><<<grid_for(nmax), kBlock, 0, s>>>(
+            N_, E_, V_, R_.p, Eu_.p, Ev_.p, oemap_.p, xp_.p, La_d1_.p,
+            flavour_ == 0 ? La_l1_.p : nullptr, tn, te, tv, c);
+        PFDR_HIP(hipGetLastError());
+        PFDR_HIP(hipMemsetAsync(red_.p, 0, 3 * sizeof(real), s));
+        mono_sum<real>(N_, tn, nullptr, 0, nullptr, red_.p, nullptr, ows_.p, s);
+        if (E_) mono_sum<real>(E_, te, nullptr, 0, nullptr, red_.p + 2, nullptr, ows_.p, s);
+        if (flavour_ == 0 && La_l1_.p)
+            mono_sum<real>(V_, tv, nullptr, 0, nullptr, red_.p + 1, nullptr, ows_.p, s);
+        k_obj_write<real><<<1, 64, 0, s>>>(red_.p, 1, flavour_ == 0 && La_l1_.p != nullptr,
+                                           ctrl_.p, Obj_.p);
+        PFDR_HIP(hipGetLastError());
+        return;
+    }
     const real *papp = nullptr;
     pull(xp_.p, sizeof(R2<real>));  // TV of boundary edges needs the ghosts' X
     if (mode_ == A_ATA) {
@@ -1980,6 +2087,13 @@ SessionBase *create_quadratic_session(const pfdr_problem *p) {
     throw std::runtime_error("dtype must be PFDR_F32 or PFDR_F64");
 }
 
+SessionBase *create_quadratic_session_sparse(const pfdr_problem *p, const pfdr_csc *A) {
+    if (!A) throw std::runtime_error("sparse A: null matrix");
+    if (p->dtype == PFDR_F32) return new QuadSession<float>(p, A);
+    if (p->dtype == PFDR_F64) return new QuadSession<double>(p, A);
+    throw std::runtime_error("dtype must be PFDR_F32 or PFDR_F64");
+}
+
 // ------------------------------------------------ drop-in entry points --
 template <typename real>
 static int quadratic_host(const char *fn, int kind, int V, int E, int N, real *X,
@@ -1988,7 +2102,7 @@ static int quadratic_host(const char *fn, int kind, int V, int E, int N, real *X
                           int positivity, real mn, real mx, int Ltype,
                           const real *L, real rho, real condMin, real difRcd,
                           real difTol, int itMax, int *it, real *Obj,
-                          real *Dif, int verbose) {
+                          real *Dif, int verbose, const pfdr_csc *csc = nullptr) {
     pfdr_problem p{};
     p.kind = kind;
     p.dtype = dtype_of<real>();
@@ -2004,7 +2118,8 @@ static int quadratic_host(const char *fn, int kind, int V, int E, int N, real *X
     try {
         CallTrace tr(fn);
         if (verbose) { printf("Initializing constants and variables... "); fflush(stdout); }
-        const std::vector<int> devs = multidev_devices(&p);
+        // (a sparse A stays on one GPU whatever the device group)
+        const std::vector<int> devs = csc ? std::vector<int>() : multidev_devices(&p);
         if (!devs.empty()) {  // partitioned across the configured devices
             if (verbose) { printf("done (%d devices).\n", (int)devs.size()); fflush(stdout); }
             int its = 0;
@@ -2013,7 +2128,7 @@ static int quadratic_host(const char *fn, int kind, int V, int E, int N, real *X
             tr.finish(V, E, N, 1, its);
             return PFDR_OK;
         }
-        std::unique_ptr<QuadSession<real>> s(new QuadSession<real>(&p));
+        std::unique_ptr<QuadSession<real>> s(new QuadSession<real>(&p, csc));
         if (verbose) { printf("done.\nPreconditioned forward-Douglas-Rachford algorithm\n"); fflush(stdout); }
         tr.setup_done();
         s->run(itMax);
@@ -2071,6 +2186,50 @@ extern "C" int pfdr_quadratic_d1_bounds_f64(int V, int E, int N, double *X,
     return quadratic_host<double>("pfdr_quadratic_d1_bounds_f64", PFDR_KIND_BOUNDS, V, E, N, X, Y,
                                   A, Eu, Ev, La_d1, nullptr, 0, min, max, Ltype, L, rho, condMin,
                                   difRcd, difTol, itMax, it, Obj, Dif, verbose);
+}
+
+// sparse A (CSC) in place of the dense matrix: pfdr_mi355x.h, "sparse A"
+extern "C" int pfdr_quadratic_d1_l1_csc_f32(int V, int E, int N, float *X, const float *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const float *val,
+    const int *Eu, const int *Ev, const float *La_d1, const float *La_l1,
+    int positivity, int Ltype, const float *L, float rho, float condMin,
+    float difRcd, float difTol, int itMax, int *it, float *Obj, float *Dif,
+    int verbose) {
+    const pfdr_csc A{nnz, colptr, rowidx, val};
+    return quadratic_host<float>("pfdr_quadratic_d1_l1_csc_f32", PFDR_KIND_L1, V, E, N, X, Y,
+                                 nullptr, Eu, Ev, La_d1, La_l1, positivity, 0.f, 0.f, Ltype, L,
+                                 rho, condMin, difRcd, difTol, itMax, it, Obj, Dif, verbose, &A);
+}
+extern "C" int pfdr_quadratic_d1_l1_csc_f64(int V, int E, int N, double *X, const double *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const double *val,
+    const int *Eu, const int *Ev, const double *La_d1, const double *La_l1,
+    int positivity, int Ltype, const double *L, double rho, double condMin,
+    double difRcd, double difTol, int itMax, int *it, double *Obj, double *Dif,
+    int verbose) {
+    const pfdr_csc A{nnz, colptr, rowidx, val};
+    return quadratic_host<double>("pfdr_quadratic_d1_l1_csc_f64", PFDR_KIND_L1, V, E, N, X, Y,
+                                  nullptr, Eu, Ev, La_d1, La_l1, positivity, 0.0, 0.0, Ltype, L,
+                                  rho, condMin, difRcd, difTol, itMax, it, Obj, Dif, verbose, &A);
+}
+extern "C" int pfdr_quadratic_d1_bounds_csc_f32(int V, int E, int N, float *X, const float *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const float *val,
+    const int *Eu, const int *Ev, const float *La_d1, float min, float max,
+    int Ltype, const float *L, float rho, float condMin, float difRcd,
+    float difTol, int itMax, int *it, float *Obj, float *Dif, int verbose) {
+    const pfdr_csc A{nnz, colptr, rowidx, val};
+    return quadratic_host<float>("pfdr_quadratic_d1_bounds_csc_f32", PFDR_KIND_BOUNDS, V, E, N, X,
+                                 Y, nullptr, Eu, Ev, La_d1, nullptr, 0, min, max, Ltype, L, rho,
+                                 condMin, difRcd, difTol, itMax, it, Obj, Dif, verbose, &A);
+}
+extern "C" int pfdr_quadratic_d1_bounds_csc_f64(int V, int E, int N, double *X, const double *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const double *val,
+    const int *Eu, const int *Ev, const double *La_d1, double min, double max,
+    int Ltype, const double *L, double rho, double condMin, double difRcd,
+    double difTol, int itMax, int *it, double *Obj, double *Dif, int verbose) {
+    const pfdr_csc A{nnz, colptr, rowidx, val};
+    return quadratic_host<double>("pfdr_quadratic_d1_bounds_csc_f64", PFDR_KIND_BOUNDS, V, E, N,
+                                  X, Y, nullptr, Eu, Ev, La_d1, nullptr, 0, min, max, Ltype, L,
+                                  rho, condMin, difRcd, difTol, itMax, it, Obj, Dif, verbose, &A);
 }
 
 // Test hook (pfdr_mi355x.h, "debug"): the edge-block records of

@@ -3089,6 +3089,38 @@ __global__ __launch_bounds__(256) void k_obj_rsq(int N,
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
+// The objective's terms for sums in the reference's order (direct mode,
+// ref :387-422: three one-accumulator loops over n, e and v): R[n]^2 at
+// tn[n], La_d1 |X_u - X_v| at te[original edge id] (emap: the edge at position
+// e, or null when the edges lie in the caller's order), La_l1 |X_v| at tv[v].
+// Subtracting La b for b < 0 is adding -(La b), so with weights >= 0 every
+// term is >= 0 and mono_sum adds them with the one-thread loop's rounding.
+template <typename real>
+__global__ __launch_bounds__(256) void k_obj_terms(
+    int N, long E, int V, const real *__restrict__ R, const int *__restrict__ Eu,
+    const int *__restrict__ Ev, const int *__restrict__ emap, const R2<real> *__restrict__ xp,
+    const real *__restrict__ La_d1, const real *__restrict__ La_l1, real *__restrict__ tn,
+    real *__restrict__ te, real *__restrict__ tv, const Ctrl<real> *ctrl) {
+    if (gated(ctrl, GATE_OBJ)) return;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < N) tn[i] = R[i] * R[i];
+    if (i < E) {
+        const real b = xp[Eu[i]].x - xp[Ev[i]].x;
+        te[emap ? emap[i] : i] = (b < real(0)) ? -(La_d1[i] * b) : La_d1[i] * b;
+    }
+    if (La_l1 && i < V) {
+        const real x = xp[i].x;
+        tv[i] = (x < real(0)) ? -(La_l1[i] * x) : La_l1[i] * x;
+    }
+}
+
+// flag[0] = 1 when some weight is negative (or NaN): its terms are not mono_sum's
+template <typename real>
+__global__ void k_negative_check(long n, const real *__restrict__ w, int *__restrict__ flag) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && !(w[i] >= real(0))) flag[0] = 1;
+}
+
 // objective partials -> red[0..2] = (data, l1, tv)
 template <typename real>
 __global__ __launch_bounds__(256) void k_obj_reduce(

@@ -362,6 +362,7 @@ bool Profiler::stats(const char *name, int *launches, double *mean_ms) const {
 // defined in the solver translation units
 SessionBase *create_quadratic_session(const pfdr_problem *p);
 SessionBase *create_simplex_session(const pfdr_problem *p);
+SessionBase *create_quadratic_session_sparse(const pfdr_problem *p, const pfdr_csc *A);
 
 }  // namespace pfdr
 
@@ -396,6 +397,31 @@ extern "C" int pfdr_session_create(pfdr_session **out, const pfdr_problem *p) {
         else
             return report_error("pfdr_session_create", "unknown problem kind");
         *out = new pfdr_session{impl};
+    });
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_session_create_sparse(pfdr_session **out, const pfdr_problem *p,
+                                          const pfdr_csc *A) {
+    const char *fn = "pfdr_session_create_sparse";
+    if (!out || !p || !A) return report_error(fn, "null argument");
+    *out = nullptr;
+    PFDR_GUARD(fn, {
+        if (p->kind != PFDR_KIND_L1 && p->kind != PFDR_KIND_BOUNDS)
+            return report_error(fn, "sparse A is for the l1 and bounds kinds (not the simplex)");
+        *out = new pfdr_session{create_quadratic_session_sparse(p, A)};
+    });
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_debug_session_csr(pfdr_session *s, int64_t *rowptr, int32_t *colidx,
+                                      void *rval) {
+    const char *fn = "pfdr_debug_session_csr";
+    if (!s) return report_error(fn, "null session");
+    PFDR_GUARD(fn, {
+        StreamScope sc(s->impl->stream, s->impl->device);
+        if (!s->impl->sparse_csr(rowptr, colidx, rval))
+            return report_error(fn, "not a sparse session");
     });
     return PFDR_OK;
 }
@@ -514,6 +540,11 @@ extern "C" int pfdr_session_query(pfdr_session *s, const char *what, int64_t *va
     else if (!strcmp(what, "graphs")) *value = s->impl->graphs;
     else if (!strcmp(what, "speculative")) *value = s->impl->speculative;
     else if (!strcmp(what, "dense_exact")) *value = s->impl->dense_exact;
+    else if (!strcmp(what, "sparse_exact")) *value = s->impl->sparse_exact;
+    else if (!strcmp(what, "sparse_nnz")) *value = s->impl->sparse_nnz;
+    else if (!strcmp(what, "sparse_seg_col")) *value = s->impl->sparse_seg_col;
+    else if (!strcmp(what, "sparse_seg_row")) *value = s->impl->sparse_seg_row;
+    else if (!strcmp(what, "sparse_csr_us")) *value = s->impl->sparse_csr_us;
     else if (!strcmp(what, "interior_edges")) *value = s->impl->interior_edges;
     else if (!strcmp(what, "device_bytes")) *value = s->impl->device_bytes;
     else return report_error("pfdr_session_query", (std::string("unknown key ") + what).c_str());

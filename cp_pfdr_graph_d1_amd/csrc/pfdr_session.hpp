@@ -76,6 +76,12 @@ class SessionBase {
     int64_t seqdif = 0;        // evolution statistic with the reference's sequential rounding
     int64_t la_uniform = 0;    // one La_d1 value for every edge: the array is not streamed
     int64_t dense_exact = 0;   // dense A: dot products in the reference's order
+    int64_t sparse_exact = 0;  // sparse A: products in the reference's order (k_spc_seq / k_spr_seq)
+    int64_t sparse_nnz = 0;    // sparse A: stored entries (0: not a sparse session)
+    int64_t sparse_seg_col = 0, sparse_seg_row = 0;  // lanes per column / row (parallel kernels)
+    int64_t sparse_csr_us = 0;  // sparse A: wall time of the CSR build at setup
+    // sparse sessions: the CSR view into host arrays (false: not a sparse session)
+    virtual bool sparse_csr(int64_t *, int32_t *, void *) { return false; }
     int64_t ghosts = 0;        // partitioned: ghost (halo) vertices of this rank
     int64_t graphs = 0;        // chunks of iterations replayed as hipGraphs
     int64_t speculative = 0;   // 1: evolution decision overlapped with the next iteration

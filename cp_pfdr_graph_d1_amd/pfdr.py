@@ -73,6 +73,9 @@ EXPORTED = (
     "pfdr_session_device_x", "pfdr_session_set_profiling", "pfdr_session_profile_filter",
     "pfdr_session_kernel_stats", "pfdr_session_sync",
     "pfdr_session_device_bytes", "pfdr_session_query", "pfdr_session_destroy",
+    "pfdr_session_create_sparse", "pfdr_debug_session_csr",
+    "pfdr_quadratic_d1_l1_csc_f32", "pfdr_quadratic_d1_l1_csc_f64",
+    "pfdr_quadratic_d1_bounds_csc_f32", "pfdr_quadratic_d1_bounds_csc_f64",
     "pfdr_comm_unique_id", "pfdr_comm_init", "pfdr_comm_destroy",
     "pfdr_comm_allreduce_max_f64", "pfdr_loopback_create", "pfdr_loopback_abort",
     "pfdr_loopback_destroy", "pfdr_plan_create", "pfdr_plan_get",
@@ -114,6 +117,12 @@ class Problem(C.Structure):
         ("vtx_label", C.c_void_p),
         ("spec", C.c_int),
     ]
+
+
+class CSCStruct(C.Structure):
+    """Mirror of ``pfdr_csc`` (include/pfdr_mi355x.h)."""
+    _fields_ = [("nnz", C.c_int64), ("colptr", C.c_void_p), ("rowidx", C.c_void_p),
+                ("val", C.c_void_p)]
 
 
 class CPProblem(C.Structure):
@@ -226,8 +235,115 @@ def _ptr(a, ct):
     return None if a is None else a.ctypes.data_as(C.POINTER(ct))
 
 
+def _is_device(a):
+    return hasattr(a, "data_ptr")
+
+
+class CSC:
+    """A sparse N-by-V observation operator in compressed sparse columns
+    (``pfdr_csc``, include/pfdr_mi355x.h): column v holds the entries
+    colptr[v] .. colptr[v+1] - 1, rowidx strictly ascending inside a column,
+    stored zeros allowed.  The arrays are numpy arrays (colptr int64, rowidx
+    int32, val float32 / float64) or torch GPU tensors of those types."""
+
+    def __init__(self, colptr, rowidx, val, N):
+        self.device = _is_device(val)
+        if self.device:
+            if not (_is_device(colptr) and _is_device(rowidx)):
+                raise TypeError("CSC: colptr, rowidx and val must all be torch GPU tensors, "
+                                "or all host arrays")
+            import torch
+            if (colptr.dtype != torch.int64 or rowidx.dtype != torch.int32 or
+                    val.dtype not in (torch.float32, torch.float64)):
+                raise TypeError("CSC: device arrays must be int64 / int32 / float32 or float64")
+            self.colptr, self.rowidx, self.val = (colptr.contiguous(), rowidx.contiguous(),
+                                                  val.contiguous())
+            self.dtype = np.dtype(np.float32 if val.dtype == torch.float32 else np.float64)
+        else:
+            self.colptr = np.ascontiguousarray(colptr, np.int64)
+            self.rowidx = np.ascontiguousarray(rowidx, np.int32)
+            val = np.ascontiguousarray(val)
+            if val.dtype not in (np.float32, np.float64):
+                val = val.astype(np.float64)
+            self.val = val
+            self.dtype = val.dtype
+        self.N = int(N)
+        self.V = int(self.colptr.shape[0]) - 1
+        self.nnz = int(self.val.shape[0])
+        self.shape = (self.N, self.V)
+
+    @classmethod
+    def from_dense(cls, A, stored=None):
+        """The nonzeros of the N-by-V matrix A, and the entries where the
+        boolean N-by-V mask ``stored`` is set whatever their value (stored
+        zeros)."""
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise ValueError("CSC.from_dense: A must be N-by-V")
+        keep = A != 0
+        if stored is not None:
+            keep = keep | np.asarray(stored, bool)
+        cols, rows = np.nonzero(keep.T)  # column by column, rows ascending
+        colptr = np.zeros(A.shape[1] + 1, np.int64)
+        np.cumsum(np.bincount(cols, minlength=A.shape[1]), out=colptr[1:])
+        return cls(colptr, rows.astype(np.int32), A[rows, cols], A.shape[0])
+
+    @classmethod
+    def from_scipy(cls, m):
+        """Any object with ``tocsc()`` giving ``indptr``, ``indices``, ``data``
+        and ``shape`` (a scipy.sparse matrix; scipy itself is not imported)."""
+        m = m.tocsc()
+        if hasattr(m, "sort_indices"):
+            m.sort_indices()
+        return cls(m.indptr, m.indices, m.data, m.shape[0])
+
+    def astype(self, dtype):
+        if self.device:
+            import torch
+            t = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
+            return CSC(self.colptr, self.rowidx, self.val.to(t), self.N)
+        return CSC(self.colptr, self.rowidx, self.val.astype(dtype, copy=False), self.N)
+
+    def to_host(self):
+        if not self.device:
+            return self
+        return CSC(self.colptr.cpu().numpy(), self.rowidx.cpu().numpy(), self.val.cpu().numpy(),
+                   self.N)
+
+    def to_device(self, device="cuda"):
+        if self.device:
+            return self
+        import torch
+        return CSC(torch.from_numpy(self.colptr).to(device), torch.from_numpy(self.rowidx).to(device),
+                   torch.from_numpy(self.val).to(device), self.N)
+
+    def to_dense(self):
+        """The N-by-V numpy matrix (stored zeros become plain zeros)."""
+        h = self.to_host()
+        A = np.zeros((h.N, h.V), h.dtype)
+        cols = np.repeat(np.arange(h.V), np.diff(h.colptr))
+        A[h.rowidx, cols] = h.val
+        return A
+
+    def struct(self):
+        """The ``pfdr_csc`` of these arrays (which must outlive its use)."""
+        if self.device:
+            return CSCStruct(self.nnz, self.colptr.data_ptr(), self.rowidx.data_ptr(),
+                             self.val.data_ptr())
+        return CSCStruct(self.nnz, self.colptr.ctypes.data, self.rowidx.ctypes.data,
+                         self.val.ctypes.data)
+
+
 class Lib:
     """Raw C-ABI calls (host pointers, synchronous)."""
+
+    @staticmethod
+    def _csc_args(A, dt):
+        """nnz, colptr, rowidx, val of a CSC for the one-call entries (host)"""
+        A = A.to_host().astype(dt)
+        keep = (A.colptr, A.rowidx, A.val)
+        return keep, (C.c_int64(A.nnz), C.c_void_p(A.colptr.ctypes.data),
+                      C.c_void_p(A.rowidx.ctypes.data), C.c_void_p(A.val.ctypes.data))
 
     def __init__(self):
         self.lib = load()
@@ -239,14 +355,21 @@ class Lib:
         X = np.array(X0, copy=True)
         ct, sfx, _ = _real(X.dtype)
         dt = X.dtype
+        csc = isinstance(A, CSC)
+        if csc:  # (A: a CSC in place of the dense matrix, N its row count)
+            _keep, aargs = self._csc_args(A, dt)
+            sfx = "csc_" + sfx
+            A = None
         Y, A, La_d1, La_l1, L = (_arr(a, dt) for a in (Y, A, La_d1, La_l1, L))
         Eu, Ev = _arr(Eu, np.int32), _arr(Ev, np.int32)
         Obj = np.zeros(itMax + 1, dt) if obj else None
         Dif = np.zeros(max(itMax, 1), dt) if dif else None
         it = C.c_int(0)
         fn = getattr(self.lib, "pfdr_quadratic_d1_l1_" + sfx)
+        if not csc:
+            aargs = (_ptr(A, ct),)
         _check(fn(C.c_int(X.size), C.c_int(Eu.size), C.c_int(N), _ptr(X, ct),
-                  _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int),
+                  _ptr(Y, ct), *aargs, _ptr(Eu, C.c_int),
                   _ptr(Ev, C.c_int), _ptr(La_d1, ct), _ptr(La_l1, ct),
                   C.c_int(positivity), C.c_int(Ltype), _ptr(L, ct), ct(rho),
                   ct(condMin), ct(difRcd), ct(difTol), C.c_int(itMax),
@@ -430,14 +553,21 @@ class Lib:
         X = np.array(X0, copy=True)
         ct, sfx, _ = _real(X.dtype)
         dt = X.dtype
+        csc = isinstance(A, CSC)
+        if csc:  # (as quadratic_d1_l1)
+            _keep, aargs = self._csc_args(A, dt)
+            sfx = "csc_" + sfx
+            A = None
         Y, A, La_d1, L = (_arr(a, dt) for a in (Y, A, La_d1, L))
         Eu, Ev = _arr(Eu, np.int32), _arr(Ev, np.int32)
         Obj = np.zeros(itMax + 1, dt) if obj else None
         Dif = np.zeros(max(itMax, 1), dt) if dif else None
         it = C.c_int(0)
         fn = getattr(self.lib, "pfdr_quadratic_d1_bounds_" + sfx)
+        if not csc:
+            aargs = (_ptr(A, ct),)
         _check(fn(C.c_int(X.size), C.c_int(Eu.size), C.c_int(N), _ptr(X, ct),
-                  _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int),
+                  _ptr(Y, ct), *aargs, _ptr(Eu, C.c_int),
                   _ptr(Ev, C.c_int), _ptr(La_d1, ct), ct(lo), ct(hi),
                   C.c_int(Ltype), _ptr(L, ct), ct(rho), ct(condMin),
                   ct(difRcd), ct(difTol), C.c_int(itMax), C.byref(it),
@@ -497,15 +627,18 @@ def PFDR_graph_quadratic_d1_l1(Y, A, Eu, Ev, La_d1, La_l1, positivity, L,
                                verbose=0, obj=False, dif=False):
     """[X, it, Obj, Dif] = PFDR_graph_quadratic_d1_l1_mex(Y, A, Eu, Ev, La_d1,
     La_l1, positivity, L, rho, condMin, difRcd, difTol, itMax, verbose)
-    (octave/mex/PFDR_graph_quadratic_d1_l1_mex.cpp): A is N-by-V."""
-    A = np.asarray(A)
+    (octave/mex/PFDR_graph_quadratic_d1_l1_mex.cpp): A is N-by-V, dense or
+    a CSC."""
+    sparse = isinstance(A, CSC)
+    A = A if sparse else np.asarray(A)
     dt = np.result_type(Y, np.float32)
     N, V = A.shape
     L = np.asarray(L, dt).ravel()
     Ltype = SCAL if L.size == 1 else DIAG
     Eu, Ev = _edges(Eu, Ev)
     return Lib().quadratic_d1_l1(
-        np.zeros(V, dt), np.asarray(Y, dt), np.asfortranarray(A, dt).ravel(order="F"),
+        np.zeros(V, dt), np.asarray(Y, dt),
+        A if sparse else np.asfortranarray(A, dt).ravel(order="F"),
         N, Eu, Ev, np.asarray(La_d1, dt), _scal_or_vec(La_l1, V, dt),
         positivity, Ltype, L, rho, condMin, difRcd, difTol, itMax, obj, dif,
         verbose)
@@ -553,14 +686,17 @@ def PFDR_graph_l22_d1_l1(Y, La_l2, Eu, Ev, La_d1, La_l1, positivity, rho,
 def PFDR_graph_quadratic_d1_bounds(Y, A, Eu, Ev, La_d1, Bnd, L, rho, condMin,
                                    difRcd, difTol, itMax, verbose=0,
                                    obj=False, dif=False):
-    """octave/mex/PFDR_graph_quadratic_d1_bounds_mex.cpp (Bnd = [min, max])."""
-    A = np.asarray(A)
+    """octave/mex/PFDR_graph_quadratic_d1_bounds_mex.cpp (Bnd = [min, max]);
+    A dense or a CSC."""
+    sparse = isinstance(A, CSC)
+    A = A if sparse else np.asarray(A)
     dt = np.result_type(Y, np.float32)
     N, V = A.shape
     L = np.asarray(L, dt).ravel()
     Eu, Ev = _edges(Eu, Ev)
     return Lib().quadratic_d1_bounds(
-        np.zeros(V, dt), np.asarray(Y, dt), np.asfortranarray(A, dt).ravel(order="F"),
+        np.zeros(V, dt), np.asarray(Y, dt),
+        A if sparse else np.asfortranarray(A, dt).ravel(order="F"),
         N, Eu, Ev, np.asarray(La_d1, dt), Bnd[0], Bnd[1],
         SCAL if L.size == 1 else DIAG, L, rho, condMin, difRcd, difTol, itMax,
         obj, dif, verbose)
@@ -747,11 +883,16 @@ def _binding_inputs(obs, source, target, edge_weight, A, l1_weight):
     if obs.dtype not in (np.float32, np.float64):
         raise TypeError("Type unknown, must be float32, float64, f4, or f8.")
     dt = obs.dtype
-    A = np.asarray(A, dt)
+    sparse = isinstance(A, CSC)
+    A = A.astype(dt) if sparse else np.asarray(A, dt)
     N = obs.size
     Eu, Ev = _edges(source, target)
     E = Eu.size
-    if A.ndim == 0 or A.size == 1 and A.ndim <= 1 and N != 1:
+    if sparse:
+        if A.N != N:
+            raise ValueError("A should be either a scalar, a vector of size N, or a N-by-V matrix ")
+        V, mode = A.V, "sparse"
+    elif A.ndim == 0 or A.size == 1 and A.ndim <= 1 and N != 1:
         V, mode = N, "identity"
     elif A.ndim == 1:
         if A.size != N:
@@ -779,7 +920,10 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
     edge_weight |x_u - x_v| + sum_v l1_weight |x_v| directly with PFDR):
       * A scalar -> identity (its value discarded); A of shape (N,) ->
         diagonal, obs and A pre-multiplied (obs*A, A*A) as the binding does
-        (:121-132); A of shape (N, V) -> the design matrix;
+        (:121-132); A of shape (N, V) -> the design matrix; a CSC -> the
+        sparse design matrix, with the Lipschitz bound ||A||_1 ||A||_inf >=
+        ||A||^2 (largest absolute column sum times largest absolute row sum)
+        in place of the dense matrix's power iteration;
       * edge_weight / l1_weight: array, or scalar broadcast to every edge /
         vertex (the binding's broadcast loops run to V for both, :134-145,
         an out-of-range write for the edge weights when E > V; here each
@@ -803,6 +947,14 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
         X, it, _, _ = lib.quadratic_d1_l1(X0, Yd, Ad, 0, Eu, Ev, ew, lw, positivity, DIAG, Ad,
                                           PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
                                           PFDR_itMax, verbose=verbose)
+    elif mode == "sparse":
+        h = A.to_host()
+        a = np.abs(h.val.astype(np.float64))
+        cols = np.repeat(np.arange(h.V), np.diff(h.colptr))
+        L = np.array([np.bincount(cols, a, h.V).max() * np.bincount(h.rowidx, a, h.N).max()], dt)
+        X, it, _, _ = lib.quadratic_d1_l1(X0, obs, h, N, Eu, Ev, ew, lw, positivity, SCAL, L,
+                                          PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
+                                          PFDR_itMax, verbose=verbose)
     else:
         Af = np.asfortranarray(A)
         L = np.array([operator_norm(Af)[0]], dt)
@@ -823,6 +975,8 @@ def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0
     vertex (uint32, as the binding) and the value of every component."""
     dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
                                                              A, l1_weight)
+    if mode == "sparse":
+        raise ValueError("cut pursuit takes a dense A: a CSC is for the PFDR entries")
     lib = Lib()
     kw = dict(positivity=positivity, CP_difTol=CP_difTol, CP_itMax=CP_itMax, rho=PFDR_rho,
               condMin=PFDR_condMin, difRcd=PFDR_difRcd, difTol=PFDR_difTol, itMax=PFDR_itMax,
@@ -846,6 +1000,8 @@ def CP_quadratic_l1_duplex(obs, source, target, edge_weight, A, l1_weight, posit
     conventions and returns."""
     dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
                                                              A, l1_weight)
+    if mode == "sparse":
+        raise ValueError("cut pursuit takes a dense A: a CSC is for the PFDR entries")
     lib = Lib()
     kw = dict(positivity=positivity, CP_difTol=CP_difTol, CP_itMax=CP_itMax, rho=PFDR_rho,
               condMin=PFDR_condMin, difRcd=PFDR_difRcd, difTol=PFDR_difTol, itMax=PFDR_itMax,
@@ -915,6 +1071,15 @@ class Session:
             self._keep.append(a)
             return C.c_void_p(a.ctypes.data)
 
+        # a CSC for A: pfdr_session_create_sparse, its arrays where the
+        # session's other arrays are (N defaults to the CSC's row count)
+        csc = None
+        if isinstance(A, CSC):
+            csc = (A.to_device() if device else A.to_host()).astype(dtype)
+            self._keep.append(csc)
+            N = N or csc.N
+            A = None
+
         p = Problem()
         p.kind, p.dtype = kind, dcode
         p.mem = PFDR_MEM_DEVICE if device else PFDR_MEM_HOST
@@ -949,9 +1114,29 @@ class Session:
         self.itMax = itMax
         self.record_obj, self.record_dif = record_obj, record_dif
         h = C.c_void_p()
-        _check(self.lib.pfdr_session_create(C.byref(h), C.byref(p)),
-               "pfdr_session_create")
+        if csc is not None:
+            self.csc = csc
+            if device:
+                _producers_done()  # (the conversions above may have queued copies)
+            cs = csc.struct()
+            _check(self.lib.pfdr_session_create_sparse(C.byref(h), C.byref(p), C.byref(cs)),
+                   "pfdr_session_create_sparse")
+        else:
+            _check(self.lib.pfdr_session_create(C.byref(h), C.byref(p)),
+                   "pfdr_session_create")
         self.h = h
+
+    def sparse_csr(self):
+        """(rowptr, colidx, rval): the CSR view a sparse session built
+        (pfdr_debug_session_csr)"""
+        rp = np.zeros(self.problem.N + 1, np.int64)
+        ci = np.zeros(self.csc.nnz, np.int32)
+        rv = np.zeros(self.csc.nnz, self.dtype)
+        _check(self.lib.pfdr_debug_session_csr(self.h, C.c_void_p(rp.ctypes.data),
+                                               C.c_void_p(ci.ctypes.data),
+                                               C.c_void_p(rv.ctypes.data)),
+               "pfdr_debug_session_csr")
+        return rp, ci, rv
 
     def run(self, iters):
         it = C.c_int(0)
@@ -1421,10 +1606,6 @@ class CPGraph:
             self.close()
         except Exception:
             pass
-
-
-def _is_device(a):
-    return hasattr(a, "data_ptr")
 
 
 class CPSolver:

@@ -269,9 +269,77 @@ int64_t pfdr_session_device_bytes(pfdr_session *s);
  * stream, 2: after them on the session stream), "edge_ratio" (1: the tiled
  * edge sweep reads each end's (c La_d1 / Aux) / Ga formed once per vertex;
  * until the first reconditioning), "vertex_pair" (> 0: the vertex sweep takes
- * two record blocks per workgroup, the value the largest block's entries). */
+ * two record blocks per workgroup, the value the largest block's entries).
+ * Sparse sessions add "sparse_nnz" (stored entries; 0 for any other session),
+ * "sparse_exact" (1: the four products add the stored entries in the
+ * reference's order, bit-exact on the densified matrix; 0: the parallel
+ * kernels), "sparse_seg_col" / "sparse_seg_row" (lanes per column / row of
+ * the parallel kernels) and "sparse_csr_us" (wall time of the CSR build). */
 int pfdr_session_query(pfdr_session *s, const char *what, int64_t *value);
 void pfdr_session_destroy(pfdr_session *s);
+
+/* ------------------------------------------------------------ sparse A -- */
+/* A (N-by-V, N > 0) in compressed sparse columns, the sparse twin of the
+ * reference's column-major layout: column v holds the entries
+ * colptr[v] .. colptr[v+1] - 1.
+ *   colptr[V+1]  non-decreasing, colptr[0] = 0, colptr[V] = nnz;
+ *   rowidx[nnz]  in [0, N), strictly ascending inside each column;
+ *   val[nnz]     of the problem's real type; stored zeros are allowed and
+ *                behave as the dense zero would.
+ * 1 <= nnz < 2^31 - 256.  The arrays are host or device memory per
+ * pfdr_problem.mem (the one-call entries: host) and are copied in.
+ *
+ * The session is the direct-mode one (Y of length N, Obj with 1/2 ||R||^2)
+ * whose four products with A -- diag(A^tA), the pseudo-inverse, R = Y - A X
+ * and -A^t R -- walk the stored entries.  While the longest column and the
+ * longest row have at most 8,192 entries, each product adds its entries in
+ * ascending index order in the real type, which gives the bytes of the
+ * reference's loops on the densified matrix as long as the iterates are
+ * finite ("sparse_exact" = 1; a recorded Obj as well, its three sums added
+ * term by term, unless a La_d1 / La_l1 is negative); longer ones take the
+ * parallel kernels (a segment of lanes per column / row, sums in double),
+ * within the dense modes' tolerances of it.  The environment variable
+ * PFDR_SPARSE_EXACT = 1 | 0 | auto, read when the session is created, forces
+ * one or the other.
+ *
+ * PFDR_ERR_ARG, with the offence named by the last-error string and before
+ * any iteration runs: N <= 0; p->A set as well; the simplex kind; nranks > 1
+ * or a communicator; a NULL array; colptr not as above; a row index out of
+ * range or not strictly ascending; a column of squared norm 0 (the reference
+ * divides by it).  The cut-pursuit entries keep their dense A. */
+typedef struct pfdr_csc {
+    int64_t nnz;
+    const int64_t *colptr;
+    const int32_t *rowidx;
+    const void *val;
+} pfdr_csc;
+int pfdr_session_create_sparse(pfdr_session **out, const pfdr_problem *p, const pfdr_csc *A);
+/* The one-call solvers above with A replaced by nnz, colptr, rowidx, val. */
+int pfdr_quadratic_d1_l1_csc_f32(int V, int E, int N, float *X, const float *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const float *val,
+    const int *Eu, const int *Ev, const float *La_d1, const float *La_l1,
+    int positivity, int Ltype, const float *L, float rho, float condMin,
+    float difRcd, float difTol, int itMax, int *it, float *Obj, float *Dif,
+    int verbose);
+int pfdr_quadratic_d1_l1_csc_f64(int V, int E, int N, double *X, const double *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const double *val,
+    const int *Eu, const int *Ev, const double *La_d1, const double *La_l1,
+    int positivity, int Ltype, const double *L, double rho, double condMin,
+    double difRcd, double difTol, int itMax, int *it, double *Obj, double *Dif,
+    int verbose);
+int pfdr_quadratic_d1_bounds_csc_f32(int V, int E, int N, float *X, const float *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const float *val,
+    const int *Eu, const int *Ev, const float *La_d1, float min, float max,
+    int Ltype, const float *L, float rho, float condMin, float difRcd,
+    float difTol, int itMax, int *it, float *Obj, float *Dif, int verbose);
+int pfdr_quadratic_d1_bounds_csc_f64(int V, int E, int N, double *X, const double *Y,
+    int64_t nnz, const int64_t *colptr, const int32_t *rowidx, const double *val,
+    const int *Eu, const int *Ev, const double *La_d1, double min, double max,
+    int Ltype, const double *L, double rho, double condMin, double difRcd,
+    double difTol, int itMax, int *it, double *Obj, double *Dif, int verbose);
+/* Debug: the CSR view a sparse session built (rowptr[N+1], colidx[nnz],
+ * rval[nnz] of the session's real type; host arrays, any may be NULL). */
+int pfdr_debug_session_csr(pfdr_session *s, int64_t *rowptr, int32_t *colidx, void *rval);
 
 /* ------------------------------------------- dense matrices (CP builder) -- */
 /* Gram matrix on the matrix cores (exact-f32 / f64 MFMA, fixed-order
