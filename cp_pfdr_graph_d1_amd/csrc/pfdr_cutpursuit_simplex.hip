@@ -19,11 +19,9 @@
 // the reference's initialize()), the loop from the state the driver holds, and
 // the download.  An entry is the three in a row; the resumable solver
 // (pfdr_cp_solver.hip) keeps the driver and runs the same loop again.
-#include <chrono>
+#include <algorithm>
 #include <cmath>
 #include <limits>
-#include <stdexcept>
-#include <vector>
 
 #include "pfdr_cp_driver.hpp"
 
@@ -31,13 +29,9 @@ namespace pfdr {
 
 namespace {
 
-#define CPS_ABI(call) CP_ABI(call)
-
 // What the last call on this thread spent where (pfdr_cp_loss_d1_simplex_stats).
 constexpr int kStatExp = 64;  // expansions whose rounds / relabels are kept one by one
-struct Stats {
-    double gradient = 0, cuts = 0, graph = 0, pfdr = 0, sums = 0, total = 0;
-    int64_t expansions = 0, rounds = 0, relabels = 0, pfdr_it = 0;
+struct Stats : CpStats {  // ncuts: the expansions
     int64_t exp_rounds[kStatExp] = {}, exp_relabels[kStatExp] = {};
 };
 thread_local Stats g_stats;
@@ -157,8 +151,7 @@ void debug_log(long n, const real *x, real *out) {
 template <typename real>
 struct SxDriver : CpDriverBase {
     Stats st;  // of the last run
-    DevBuf<int> off{2};
-    DevBuf<real> one{1};
+    CpSeqSum<real> seq_sum{s};
     // the resident problem
     DevBuf<real> dQ;
     real al = real(0);
@@ -167,29 +160,6 @@ struct SxDriver : CpDriverBase {
     DevBuf<int> dCv;
     real obj = real(0);  // the functional at the state, when known
     bool obj_known = false;
-
-    // ((0 + x[0]) + x[1]) + ... in real
-    real seq_sum(const real *x, long n) {
-        if (n <= 0) return real(0);
-        if (n >= (1L << 31)) throw std::runtime_error("sum of 2^31 or more terms");
-        const int h[2] = {0, (int)n};
-        PFDR_HIP(hipMemcpyAsync(off.p, h, sizeof h, hipMemcpyHostToDevice, s));
-        ordered_segment_sums<real>(1, off.p, nullptr, x, one.p, s);
-        real r;
-        PFDR_HIP(hipMemcpyAsync(&r, one.p, sizeof(real), hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-        return r;
-    }
-
-    template <typename T>
-    void up(DevBuf<T> &d, const T *h, size_t n, HostPins &hp) {
-        d.alloc(n ? n : 1);
-        if (n) hp.copy(d.p, h, n * sizeof(T), hipMemcpyHostToDevice);
-    }
-
-    static double since(clock::time_point t) {
-        return std::chrono::duration<double>(clock::now() - t).count();
-    }
 
     // the functional at (Cv, rP) with the reduced graph given (:870-917)
     real objective(int K, int V, real al, int rV, int rE, const int *Cv, const real *rP,
@@ -239,23 +209,23 @@ struct SxDriver : CpDriverBase {
             cp_take(dLa, (const real *)p.La_d1, (size_t)E, p.mem, hp, s);
             hp.release();
         }
-        CPS_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, nullptr, PFDR_MEM_DEVICE));
-        CPS_ABI(pfdr_cpgraph_simplex_setup(g, K, (double)al, dQ.p, PFDR_MEM_DEVICE));
+        CP_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, nullptr, PFDR_MEM_DEVICE));
+        CP_ABI(pfdr_cpgraph_simplex_setup(g, K, (double)al, dQ.p, PFDR_MEM_DEVICE));
 
         // ---- initialize (:96-116): one component, its rP from the observations
         rV = 1;
         drP.alloc((size_t)K);
         drQ.alloc((size_t)K);
-        CPS_ABI(pfdr_cpgraph_simplex_observations(g, drP.p, drQ.p, nullptr, PFDR_MEM_DEVICE));
+        CP_ABI(pfdr_cpgraph_simplex_observations(g, drP.p, drQ.p, nullptr, PFDR_MEM_DEVICE));
         dCv.alloc(V);
-        CPS_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+        CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
         // the functional itself, as every later Obj[k] with rV = 1
         obj_known = false;
         if (want_obj) {
             const auto t = clock::now();
             obj = objective(K, V, al, 1, 0, dCv.p, drP.p, drQ.p, dQ.p, nullptr, nullptr, nullptr);
             obj_known = true;
-            st.sums += since(t);
+            setup_sums = since(t);
         }
     }
 
@@ -264,24 +234,15 @@ struct SxDriver : CpDriverBase {
         drP.alloc((size_t)rV * K);
         PFDR_HIP(hipMemcpyAsync(drP.p, x, sizeof(real) * rV * K, hipMemcpyDeviceToDevice, s));
         PFDR_HIP(hipStreamSynchronize(s));
-        CPS_ABI(pfdr_cpgraph_simplex_set_values(g, drP.p, PFDR_MEM_DEVICE));
-        CPS_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
+        CP_ABI(pfdr_cpgraph_simplex_set_values(g, drP.p, PFDR_MEM_DEVICE));
+        CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr, PFDR_MEM_DEVICE));
         obj_known = false;
     }
     const void *values() const override { return drP.p; }
     const void *residual() const override { return nullptr; }
     void forget_objective() override { obj_known = false; }
     void stats(double *seconds, int64_t *counts) const override {
-        if (seconds) {
-            const double v[6] = {st.gradient, st.cuts, st.graph, st.pfdr, st.sums, st.total};
-            for (int i = 0; i < 6; i++) seconds[i] = v[i];
-        }
-        if (counts) {
-            counts[0] = st.expansions;
-            counts[1] = st.rounds;
-            counts[2] = st.relabels;
-            counts[3] = st.pfdr_it;
-        }
+        cp_write_stats(st, seconds, counts);
     }
 
     void loop(clock::time_point t0, const pfdr_cp_params &q, int *CP_it_out, double *Time,
@@ -346,29 +307,29 @@ struct SxDriver : CpDriverBase {
             if (it == CP_itMax || dif < CP_difTol) break;
             // steepest cuts (:327-618)
             auto t = clock::now();
-            CPS_ABI(pfdr_cpgraph_simplex_gradient(g, (double)eps, nullptr, nullptr,
-                                                  PFDR_MEM_DEVICE));
+            CP_ABI(pfdr_cpgraph_simplex_gradient(g, (double)eps, nullptr, nullptr,
+                                                 PFDR_MEM_DEVICE));
             st.gradient += since(t);
             t = clock::now();
             for (int n = 1; n < K; n++) {
                 int64_t rounds = 0, relabels = 0;
-                CPS_ABI(pfdr_cpgraph_simplex_capacities(g, n, dtr.p, drc.p, PFDR_MEM_DEVICE));
-                CPS_ABI(pfdr_cpgraph_mincut(g, PFDR_ARCS_FORWARD, dtr.p, drc.p, PFDR_MEM_DEVICE,
-                                            dseg.p, nullptr, &rounds));
-                CPS_ABI(pfdr_cpgraph_mincut_relabels(g, &relabels));
-                CPS_ABI(pfdr_cpgraph_simplex_expand(g, n, dseg.p, PFDR_MEM_DEVICE));
-                if (st.expansions < kStatExp) {
-                    st.exp_rounds[st.expansions] = rounds;
-                    st.exp_relabels[st.expansions] = relabels;
+                CP_ABI(pfdr_cpgraph_simplex_capacities(g, n, dtr.p, drc.p, PFDR_MEM_DEVICE));
+                CP_ABI(pfdr_cpgraph_mincut(g, PFDR_ARCS_FORWARD, dtr.p, drc.p, PFDR_MEM_DEVICE,
+                                           dseg.p, nullptr, &rounds));
+                CP_ABI(pfdr_cpgraph_mincut_relabels(g, &relabels));
+                CP_ABI(pfdr_cpgraph_simplex_expand(g, n, dseg.p, PFDR_MEM_DEVICE));
+                if (st.ncuts < kStatExp) {
+                    st.exp_rounds[st.ncuts] = rounds;
+                    st.exp_relabels[st.ncuts] = relabels;
                 }
-                st.expansions++;
+                st.ncuts++;
                 st.rounds += rounds;
                 st.relabels += relabels;
             }
             st.cuts += since(t);
             t = clock::now();
             int w = 0, n = 0;
-            CPS_ABI(pfdr_cpgraph_simplex_activate(g, &w));
+            CP_ABI(pfdr_cpgraph_simplex_activate(g, &w));
             if (verbose) printf("\t%d new activated edge(s).\n", w);
             if (w == 0) {  // :631-639
                 st.graph += since(t);
@@ -381,21 +342,21 @@ struct SxDriver : CpDriverBase {
                 continue;
             }
             // reduced graph and observations (:643-766)
-            CPS_ABI(pfdr_cpgraph_components(g, &rV));
-            CPS_ABI(pfdr_cpgraph_reduced_graph(g, (double)eps, &rE));
-            CPS_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr,
-                                                PFDR_MEM_DEVICE));
+            CP_ABI(pfdr_cpgraph_components(g, &rV));
+            CP_ABI(pfdr_cpgraph_reduced_graph(g, (double)eps, &rE));
+            CP_ABI(pfdr_cpgraph_get_components(g, nullptr, dCv.p, nullptr, nullptr,
+                                               PFDR_MEM_DEVICE));
             rEu.alloc(rE > 0 ? rE : 1);
             rEv.alloc(rE > 0 ? rE : 1);
             rLa.alloc(rE > 0 ? rE : 1);
-            CPS_ABI(pfdr_cpgraph_get_reduced(g, rEu.p, rEv.p, rLa.p, nullptr, PFDR_MEM_DEVICE));
+            CP_ABI(pfdr_cpgraph_get_reduced(g, rEu.p, rEv.p, rLa.p, nullptr, PFDR_MEM_DEVICE));
             const size_t rVK = (size_t)rV * K;
             drP.alloc(rVK);
             drQ.alloc(rVK);
             drLaf.alloc(rV);
-            CPS_ABI(pfdr_cpgraph_simplex_observations(g, drP.p, drQ.p,
-                                                      al > real(0) ? drLaf.p : nullptr,
-                                                      PFDR_MEM_DEVICE));
+            CP_ABI(pfdr_cpgraph_simplex_observations(g, drP.p, drQ.p,
+                                                     al > real(0) ? drLaf.p : nullptr,
+                                                     PFDR_MEM_DEVICE));
             st.graph += since(t);
             // PFDR from the components' own optima (:778-780)
             t = clock::now();
@@ -420,25 +381,12 @@ struct SxDriver : CpDriverBase {
                 p.difTol = difTol;
                 p.itMax = itMax;
                 p.verbose = verbose;
-                pfdr_session *ses = nullptr;
-                CPS_ABI(pfdr_session_create(&ses, &p));
-                struct SHold {
-                    pfdr_session *q;
-                    ~SHold() { pfdr_session_destroy(q); }
-                } sh{ses};
-                int pit = 0;
-                CPS_ABI(pfdr_session_run(ses, itMax, &pit));
-                CPS_ABI(pfdr_session_sync(ses));
-                st.pfdr_it += pit;
-                const void *x = pfdr_session_device_x(ses);
-                if (!x) throw CpAbiFail{PFDR_ERR_STATE};
-                PFDR_HIP(hipMemcpyAsync(drP.p, x, sizeof(real) * rVK, hipMemcpyDeviceToDevice, s));
-                PFDR_HIP(hipStreamSynchronize(s));
+                st.pfdr_it += cp_pfdr_solve(p, sizeof(real) * rVK, s);
             }
             st.pfdr += since(t);
             t = clock::now();
-            CPS_ABI(pfdr_cpgraph_simplex_set_values(g, drP.p, PFDR_MEM_DEVICE));
-            CPS_ABI(pfdr_cpgraph_simplex_merge(g, (double)eps, &n));
+            CP_ABI(pfdr_cpgraph_simplex_set_values(g, drP.p, PFDR_MEM_DEVICE));
+            CP_ABI(pfdr_cpgraph_simplex_merge(g, (double)eps, &n));
             if (verbose) printf("\t%d deactivated edge(s).\n", n);
             st.graph += since(t);
             // iterate evolution (:808-866); the last partition then becomes this one,
@@ -483,10 +431,7 @@ struct SxDriver : CpDriverBase {
 
     void download(int *rV_out, int *Cv, void *rP_out) override {
         *rV_out = rV;
-        HostPins hp(s);
-        hp.copy(Cv, dCv.p, sizeof(int) * V, hipMemcpyDeviceToHost);
-        hp.copy(rP_out, drP.p, sizeof(real) * rV * K, hipMemcpyDeviceToHost);
-        hp.release();
+        cp_download<real>(s, V, dCv.p, Cv, drP.p, (size_t)rV * K, rP_out);
     }
 };
 
@@ -499,35 +444,14 @@ int cps_entry(const char *fn, int K, int V, int E, real al, int *rV, int *Cv, re
         (E > 0 && (!Eu || !Ev || !La_d1)))
         return report_error(fn, "invalid arguments");
     if (!(al >= real(0) && al <= real(1))) return report_error(fn, "al must lie in [0, 1]");
-    try {
-        const auto t0 = std::chrono::steady_clock::now();
-        g_stats = Stats{};
-        SxDriver<real> d;
-        struct Keep {  // what the call spent, also when it fails half way
-            SxDriver<real> &d;
-            ~Keep() { g_stats = d.st; }
-        } keep{d};
-        pfdr_cp_problem p{};
-        p.kind = PFDR_KIND_SIMPLEX;
-        p.mem = PFDR_MEM_HOST;
-        p.V = V, p.E = E, p.K = K;
-        p.Y = Q, p.Eu = Eu, p.Ev = Ev, p.La_d1 = La_d1;
-        p.al = al;
-        const pfdr_cp_params q{CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose};
-        d.setup(p, Obj != nullptr);
-        const double init_sums = d.st.sums;
-        d.loop(t0, q, CP_it, Time, Obj, Dif);
-        d.download(rV, Cv, rP);
-        d.st.sums += init_sums;
-        d.st.total = SxDriver<real>::since(t0);
-    } catch (const CpAbiFail &f) {
-        return f.status;
-    } catch (const HipError &h) {
-        return report_error(fn, h);
-    } catch (const std::exception &ex) {
-        return report_error(fn, ex.what());
-    }
-    return PFDR_OK;
+    pfdr_cp_problem p{};
+    p.kind = PFDR_KIND_SIMPLEX;
+    p.mem = PFDR_MEM_HOST;
+    p.V = V, p.E = E, p.K = K;
+    p.Y = Q, p.Eu = Eu, p.Ev = Ev, p.La_d1 = La_d1;
+    p.al = al;
+    const pfdr_cp_params q{CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose};
+    return cp_run_entry<SxDriver<real>>(fn, &g_stats, p, q, rV, Cv, rP, CP_it, Time, Obj, Dif);
 }
 
 }  // namespace
@@ -577,17 +501,8 @@ extern "C" int pfdr_cp_loss_d1_simplex_stats(double *seconds, int64_t *counts,
                                              int64_t *exp_rounds, int64_t *exp_relabels,
                                              int n_exp) {
     const pfdr::Stats &st = pfdr::g_stats;
-    if (seconds) {
-        const double v[6] = {st.gradient, st.cuts, st.graph, st.pfdr, st.sums, st.total};
-        for (int i = 0; i < 6; i++) seconds[i] = v[i];
-    }
-    if (counts) {
-        counts[0] = st.expansions;
-        counts[1] = st.rounds;
-        counts[2] = st.relabels;
-        counts[3] = st.pfdr_it;
-    }
-    const int64_t kept = st.expansions < pfdr::kStatExp ? st.expansions : pfdr::kStatExp;
+    pfdr::cp_write_stats(st, seconds, counts);
+    const int64_t kept = st.ncuts < pfdr::kStatExp ? st.ncuts : pfdr::kStatExp;
     for (int i = 0; i < n_exp; i++) {
         if (exp_rounds) exp_rounds[i] = i < kept ? st.exp_rounds[i] : -1;
         if (exp_relabels) exp_relabels[i] = i < kept ? st.exp_relabels[i] : -1;

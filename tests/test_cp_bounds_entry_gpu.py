@@ -1,5 +1,5 @@
 """The bounds driver's one-call cut pursuit (pfdr_cp_quadratic_d1_bounds,
-csrc/pfdr_cutpursuit_bounds.hip) pinned on every path of its loop.
+the bounds flavour of csrc/pfdr_cutpursuit.hip) pinned on every path of its loop.
 
 a. N = 0: Cv, rX and CP_it equal the reference's recorded iterations
    (tests/golden/cp_bounds_*.npz) bit for bit, for every truncation

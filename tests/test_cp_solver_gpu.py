@@ -6,6 +6,7 @@
 3. a split run is the uninterrupted one (N = 0, N = -V), Obj and Dif included;
 4. dense restarts against the twin, one of them flipping preAt; R recomputed;
 5. a state exported and imported (host and device arrays) continues alike;
+   a dense A given as device arrays runs as the host arrays do;
 6. a change of penalties is a restart of a solver created with them;
 7. the partition import against the step API, a union-find and the twin;
 8. rejected states leave the solver unchanged;
@@ -212,6 +213,25 @@ def test_state_round_trip(gpu_lib, kind, device):
         h = SC.solver(p)
         assert out_equal(run(h, p), first) == []
         h.close()
+
+
+@pytest.mark.parametrize("kind,mod", [("l1", RC), ("duplex", DRC), ("bounds", BRC)],
+                         ids=("l1", "duplex", "bounds"))
+def test_dense_device_arrays_are_the_host_ones(gpu_lib, kind, mod):
+    """a dense A (direct12, N = 12) given as device arrays: the bytes of the
+    host-array solver, Obj[0] (the sums of initialize()) and R included"""
+    p = mod.problem("direct12", F32)
+    assert p["kind"] == kind and p["N"] == 12
+    outs = []
+    for device in (True, False):
+        s = SC.solver(p, device=device)
+        out = run(s, p, CP_itMax=3)
+        outs.append((out, s.state()["R"]))
+        s.close()
+    (dev, dev_R), (host, host_R) = outs
+    assert dev[3] is not None and dev[4] is not None
+    assert out_equal(dev, host) == []
+    assert same_bytes(dev_R, host_R)
 
 
 # ----------------------------------------------------- 6. penalty path --
