@@ -59,6 +59,9 @@ template <> struct Lim<double> {
     static constexpr double huge = __builtin_huge_val();
 };
 
+template <typename real>
+inline int dtype_of() { return sizeof(real) == 4 ? PFDR_F32 : PFDR_F64; }
+
 // ---------------------------------------------------- loop control block --
 // Device-resident iteration state.  The per-iteration kernels return at once
 // when `halt` is set, so the host can enqueue iterations in chunks and read
@@ -280,6 +283,18 @@ void upload(DevBuf<T> &d, const T *h, size_t n, hipStream_t s) {
     if (!h || !n) { d.release(); return; }
     d.alloc(n);
     PFDR_HIP(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
+}
+
+// A caller's array (host or device, pfdr_problem.mem) into a fresh device
+// buffer; host arrays through pins (nullptr stays nullptr).
+template <typename real>
+void copy_in(DevBuf<real> &d, const void *src, size_t n, int mem, hipStream_t s, HostPins &pins) {
+    if (!src || !n) { d.release(); return; }
+    d.alloc(n);
+    if (mem == PFDR_MEM_DEVICE)
+        PFDR_HIP(hipMemcpyAsync(d.p, src, n * sizeof(real), hipMemcpyDeviceToDevice, s));
+    else
+        pins.copy(d.p, src, n * sizeof(real), hipMemcpyHostToDevice);
 }
 
 }  // namespace pfdr

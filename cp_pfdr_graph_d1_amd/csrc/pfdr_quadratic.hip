@@ -4,32 +4,15 @@
 // of a 1-D vertex-range partition (pfdr_halo.hpp).  Kernels: see
 // pfdr_quadratic_kernels.hpp.
 #include <cstring>
-#include <map>
 #include <stdexcept>
 
-
-#include "pfdr_halo.hpp"
+#include "pfdr_loop.hpp"
 #include "pfdr_order.hpp"
 #include "pfdr_quadratic_kernels.hpp"
 #include "pfdr_sort.hpp"
 #include "pfdr_sparse.hpp"
 
 namespace pfdr {
-
-template <typename real>
-static void copy_in(DevBuf<real> &d, const void *src, size_t n, int mem, hipStream_t s,
-                    HostPins &pins) {
-    if (!src || !n) { d.release(); return; }
-    d.alloc(n);
-    if (mem == PFDR_MEM_DEVICE)
-        PFDR_HIP(hipMemcpyAsync(d.p, src, n * sizeof(real), hipMemcpyDeviceToDevice, s));
-    else
-        pins.copy(d.p, src, n * sizeof(real), hipMemcpyHostToDevice);
-}
-
-template <typename real>
-static int dtype_of() { return sizeof(real) == 4 ? PFDR_F32 : PFDR_F64; }
-
 
 // d <- d[map] (map[i] = source index of element i)
 template <typename T>
@@ -112,35 +95,31 @@ __global__ void k_remap_push(long n, long E, const unsigned *__restrict__ inv,
 
 
 template <typename real>
-class QuadSession final : public SessionBase {
+class QuadSession final : public IterLoop<real> {
   public:
     explicit QuadSession(const pfdr_problem *p, const pfdr_csc *csc = nullptr);
     ~QuadSession() override {
-        if (hctrl_) {
-            (void)hipStreamSynchronize(stream);  // no control-block copy in flight
-            pinned_small_put(hctrl_);
-        }
-        for (Ctrl<real> *c : snap_) if (c) pinned_small_put(c);
-        for (hipEvent_t e : snapev_) if (e) (void)hipEventDestroy(e);
+        this->close();  // (the loop's streams are drained before any buffer goes)
         for (hipEvent_t e : ev_) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : evv_) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : evd_) if (e) (void)hipEventDestroy(e);
         if (comm_) (void)hipStreamDestroy(comm_);
-        if (evs_) {
-            (void)hipStreamSynchronize(evs_);
-            (void)hipStreamDestroy(evs_);
-        }
-        drop_graphs();
     }
-    int run(int iters) override;
-    int run_pipelined(int target);
     void result(void *X_host, int *it, void *Obj_host, void *Dif_host) override;
     void *device_x() override;
 
   private:
+    using L = IterLoop<real>;
+    using L::stream, L::prof, L::device, L::device_bytes, L::interior_edges;
+    using L::reordered, L::split_blocks, L::tiled_blocks, L::record_blocks, L::slot_patterns;
+    using L::edge_ratio, L::vertex_pair, L::ustaged, L::symv, L::tiny, L::fused, L::padded;
+    using L::seqdif, L::la_uniform, L::dense_exact, L::sparse_exact, L::sparse_nnz, L::ghosts;
+    using L::sparse_seg_col, L::sparse_seg_row, L::sparse_csr_us, L::speculative;
+    using L::halo_, L::evtr_, L::ctrl_, L::hctrl_, L::itMax_, L::verbose_, L::it_;
+    using L::stopped_, L::chunk_, L::tiny_, L::graphs_ok_, L::capturable_, L::kSpecMax;
+    using L::spec_, L::sd_, L::seqdif_, L::chain_, L::route_, L::dws_, L::red_;
+    using L::push_ctrl, L::drop_graphs, L::evolution_sum;
     // problem
     int flavour_;  // 0 l1, 1 bounds
-    int V_, Vg_, N_, mode_, itMax_, verbose_;
+    int V_, Vg_, N_, mode_;
     long E_;
     real rho_, condMin_, difTol_, difRcd2_, cap_;
     int prox_, positivity_;
@@ -175,51 +154,19 @@ class QuadSession final : public SessionBase {
     // terms (X_ - X)^2 and X^2 in the caller's vertex order, two binade-scan
     // sums (mono_sum) replace the tree of k_reduce_decide, k_decide decides
     int evo_ = PFDR_EVOLUTION_AUTO;
-    bool seqdif_ = false;
     long tstride_ = 0;
     DevBuf<real> terms_;
-    DevBuf<char> dws_;
-    // partitioned sessions: the terms of the ranks in rank order are summed
-    // rank to rank (ChainSum); a relabelled partition (lab_) first routes
-    // every vertex's terms to the rank whose caller-order slice holds its
-    // label (TermRoute: one all-to-all of ~V/N items per rank), then chains
-    ChainSum<real> chain_;
-    TermRoute<real> route_;
-    // the transport of the evolution sums: a speculative partition's own
-    // (Transport::split), so they run beside the next iteration's exchanges
-    std::unique_ptr<Transport> evtr_;
-    Transport &etr() { return evtr_ ? *evtr_ : *halo_->tr; }
     void seq_evolution(real *terms, const real *part, hipStream_t s);
     void sweeps(const Ctrl<real> *c);  // halo pull, edge sweep, halo push, vertex sweep
-    // Speculative iteration (sequential evolution, no reconditioning
-    // (difRcd = 0), no objective record, identity / diagonal A; one GPU or a
-    // partition): the evolution sums and the decision on iteration t run on
-    // a second stream (evs_) while iterations t + 1 ... t + D - 1 sweep;
-    // iteration t + D waits for that decision (depth D = sd_: 2 on one GPU;
-    // 4 on a partition of three or more ranks, whose rank-to-rank evolution
-    // chain, run there over a split transport (evtr_) beside the halo
-    // exchanges, takes several of a rank's iterations).  X cycles through D
-    // buffers (iteration t reads xpb(t - 1), writes xpb(t)) and the terms
-    // through D, so when the decision on t stops the loop, X_t is intact in
-    // xpb(t) and the speculative iterations after it (their Z, their X in the
-    // other buffers) are simply discarded: the iterate, iteration count and
-    // Dif are the sequential loop's, bit for bit.
-    static constexpr int kSpecMax = 4;
-    bool spec_ = false;
-    int sd_ = 2;
-    int it0_ = 0;  // completed iterations when the captured / launched bodies start
+    // Speculative iteration (IterLoop::spec_; here: difRcd = 0, identity /
+    // diagonal A): X cycles through D buffers (iteration t reads xpb(t - 1),
+    // writes xpb(t)) and the terms and their block sums through D
     DevBuf<R2<real>> xpx_[kSpecMax - 1];  // X buffers 1 .. D - 1 (0 is xp_)
     R2<real> *xpb(int t) { return spec_ && t % sd_ ? xpx_[t % sd_ - 1].p : xp_.p; }
     R2<real> *xr_ = nullptr, *xw_ = nullptr;  // the sweeps' read / write (X, P)
-    hipStream_t evs_ = nullptr;  // the decisions' stream (null: PFDR_SPEC_SERIAL, the session's)
-    hipStream_t evs() const { return evs_ ? evs_ : stream; }
-    hipEvent_t evv_[kSpecMax] = {}, evd_[kSpecMax] = {};
-    // run_pipelined: the control block's snapshots after two chunks in flight
-    Ctrl<real> *snap_[2] = {};
-    hipEvent_t snapev_[2] = {};
-    void body_spec(int i, int n);
+    void spec_sweeps(int t, int b) override;
+    void spec_decide(int b, hipStream_t s) override;
     static constexpr long kSeqDifMin = 1L << 17;  // AUTO: sums of at least this many terms
-    std::unique_ptr<Halo> halo_;  // partition plan (null on one GPU)
     // internal relabelling (pfdr_order.hpp): order_[new] = old, where_[old] = new,
     // emap_[edge position] = original edge id (setup only)
     bool reordered_ = false;
@@ -240,7 +187,7 @@ class QuadSession final : public SessionBase {
     int vpair_cap_ = 0;  // pair vertex sweep: entries of the largest record block (0: off)
     bool rat_on_ = false;  // rr_ formed at setup (see rat())
     real cw_ = real(0);
-    DevBuf<real> R_, vpart_, opart_, Obj_, Dif_, red_, csum_;
+    DevBuf<real> R_, vpart_, opart_, Obj_, Dif_, csum_;
     DevBuf<double> Rpart_;  // k_rows_partial's double partials
     DevBuf<real> Rsum_, xfull_;  // dense A on a partition: summed A X, gathered X
     // relabelled partition (pfdr_problem.vtx_label): the caller's label of
@@ -251,7 +198,6 @@ class QuadSession final : public SessionBase {
     long v0_ = 0, Vglob_ = 0;
     DevBuf<long long> ccnt_;
     DevBuf<int> cnt_part_;
-    DevBuf<Ctrl<real>> ctrl_;
     Incidence inc_;
     HostPins pins_;  // caller arrays pinned for the setup copies
     // split incidence (edges sorted by u): u-run offsets, per-vertex order
@@ -275,29 +221,7 @@ class QuadSession final : public SessionBase {
     void build_tiles();
     void build_patterns(const unsigned short *d2, long n);
     void build_tile_runs();
-    Ctrl<real> *hctrl_ = nullptr;  // pinned mirror
     int nbv_, nbe_, nbn_, rows_nb_, rows_cpb_;
-    int it_ = 0;
-    bool stopped_ = false;
-    int chunk_ = 32;
-    int next_print_ = 0;
-    // hipGraph of a chunk of iterations (single GPU, unprofiled): a replayed
-    // kernel boundary costs ~1.6 us of GPU time, a launched one ~2.8 us
-    // (profiles/r2/r2d_launch_gap.log) -- the difference is a large share of
-    // an iteration of a small graph.  Re-captured after a reconditioning
-    // (new kernel arguments).
-    bool graphs_ok_ = false;
-    bool capturable_ = false;  // prepare(): graphs of any run length on request
-    std::map<int, hipGraphExec_t> graphs_;
-    void run_bodies(int n);
-    hipGraphExec_t chunk_graph(int n);
-  public:
-    void prepare(int iters) override;
-  private:
-    void drop_graphs() {
-        for (auto &kv : graphs_) (void)hipGraphExecDestroy(kv.second);
-        graphs_.clear();
-    }
 
     void setup_graph(const pfdr_problem *p);
     void amplitude(bool init);
@@ -306,11 +230,10 @@ class QuadSession final : public SessionBase {
     void forward_dense(int gate);
     void gradient();
     void objective();
-    void body(int i, int n);  // i-th of n bodies of a chunk
-    void push_ctrl();
-    void pull_ctrl();
-    void wait_stream();
-    void print_progress();
+    void body(int i, int n) override;
+    void recondition() override;
+    void print_progress() override;
+    bool gated() const override { return track_ || rec_obj_; }
     void pull(void *base, int eb) { if (halo_) halo_->pull(base, eb, stream); }
     // halo / compute overlap (partitioned sessions): the halo exchanges run
     // on comm_ while the sweeps of interior edges [elo_, ehi_) and interior
@@ -345,8 +268,7 @@ class QuadSession final : public SessionBase {
     VArgs<real> vargs(int bbeg, int bend, const Ctrl<real> *c);
     // small single-GPU graphs: a chunk of iterations in one workgroup launch
     // (k_tiny_iterate; PFDR_TINY = max edges, 0 = off)
-    bool tiny_ = false;
-    void tiny_chunk(int n);
+    void tiny_chunk(int n) override;
     const real *full_x();  // X of every vertex (A^tA mode), gathered over the ranks
     // A^tA mode on one GPU with an exactly symmetric matrix: products from the
     // block upper triangle (k_symv_tiles / k_symv_finish, half the bytes)
@@ -609,13 +531,8 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
     if (mode_ == A_DIRECT && halo_) Rsum_.alloc(N_);
 
     // control block
-    ctrl_.alloc(1);
-    static_assert(sizeof(Ctrl<real>) <= kPinnedSmall, "control block");
-    hctrl_ = static_cast<Ctrl<real> *>(pinned_small_get());
-    std::memset(hctrl_, 0, sizeof(Ctrl<real>));
+    this->alloc_ctrl();
     const real difTol2 = difTol_ * difTol_;
-    hctrl_->obj_it = -1;
-    hctrl_->itMax = itMax_;
     hctrl_->dif = difTol2 > difRcd2_ ? difTol2 : difRcd2_;  // ref :342
     hctrl_->difTol = difTol2;
     hctrl_->difRcd = difRcd2_;
@@ -769,17 +686,13 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
         const int smode = spec_mode(p);
         spec_ = difRcd2_ == real(0) && !rec_obj_ && (mode_ == A_IDENT || mode_ == A_DIAG) &&
                 smode != PFDR_SPEC_OFF;
-        const bool serial = smode == PFDR_SPEC_SERIAL;
-        if (spec_ && halo_ && !serial) {
-            evtr_ = halo_->tr->split(s);  // (a collective: every rank decides alike)
+        if (spec_) {
+            this->spec_setup(smode == PFDR_SPEC_SERIAL);
             // the halo exchanges stay on the session stream: a third stream
             // for them (overlap_) shared a hardware queue with the evolution
             // stream, so the next pull waited behind the whole evolution chain
             // (1-rank RCCL headline_conv 0.686 ms/iter against 0.557 on one GPU)
-            overlap_ = false;
-        }
-        if (spec_) {
-            sd_ = halo_ && halo_->tr->nranks >= 3 ? 4 : 2;
+            if (evtr_) overlap_ = false;
             DevBuf<real> t2((size_t)sd_ * 2 * tstride_);  // terms of D iterations
             std::swap(terms_.p, t2.p);
             std::swap(terms_.n, t2.n);
@@ -791,12 +704,6 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
                 PFDR_HIP(hipMemcpyAsync(xpx_[k].p, xp_.p, sizeof(R2<real>) * (Vg_ + 2),
                                         hipMemcpyDeviceToDevice, s));
             }
-            if (!serial) PFDR_HIP(hipStreamCreateWithFlags(&evs_, hipStreamNonBlocking));
-            for (int k = 0; k < sd_; k++) {
-                PFDR_HIP(hipEventCreateWithFlags(&evv_[k], hipEventDisableTiming));
-                PFDR_HIP(hipEventCreateWithFlags(&evd_[k], hipEventDisableTiming));
-            }
-            speculative = serial ? 2 : 1;
         }
     }
     {
@@ -818,28 +725,12 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
         edge_ratio = 1;
     }
     xr_ = xw_ = xp_.p;
-    // a speculative session launches directly on its two streams: the
-    // decision's kernels must run BESIDE the next sweeps, and a replayed
-    // graph ran its branches one after the other (headline_conv 0.852
-    // ms/iter with the graph, r4h)
-    if (spec_) graphs_ok_ = capturable_ = false;
     if (!seqdif_ || !reordered_) order_.release();  // inputs are in the internal labels now
     acc(where_.n * 4 + amp_orig_.n * sizeof(real) + order_.n * 4 + terms_.n * sizeof(real) + dws_.n);
     acc(route_.slice.n * sizeof(real) + route_.chain.ws.n + chain_.ws.n + ampg_.n * sizeof(real) +
         (xpx_[0].n + xpx_[1].n + xpx_[2].n) * sizeof(R2<real>));
     acc(sl_.n * 4 + wzp_.n * sizeof(real) + pidx_.n * 4 + (xpe_.n + gie_.n) * sizeof(R2<real>));
-    // the chunk graph is part of the setup (instantiation costs ~0.1-1 ms,
-    // which a small solve timed to tolerance would otherwise pay in its loop)
-    if (graphs_ok_) {
-        try {
-            (void)chunk_graph(chunk_);
-        } catch (const std::exception &) {
-            if (!halo_) throw;
-            graphs_ok_ = capturable_ = false;  // this transport would not capture: launch directly
-            (void)hipGetLastError();
-        }
-    }
-    graphs = graphs_ok_ ? 1 : 0;
+    this->instantiate_setup_graph();
 }
 
 template <typename real>
@@ -1232,27 +1123,6 @@ void QuadSession<real>::build_split() {
     split_blocks = n;
     if (!n) { mask_.release(); oidx_.release(); blkok_.release(); }  // uptr_ serves the edge sweep
     ustaged = us_ ? 1 : 0;
-}
-
-template <typename real>
-void QuadSession<real>::push_ctrl() {
-    PFDR_HIP(hipMemcpyAsync(ctrl_.p, hctrl_, sizeof(Ctrl<real>), hipMemcpyHostToDevice, stream));
-}
-template <typename real>
-void QuadSession<real>::pull_ctrl() {
-    PFDR_HIP(hipMemcpyAsync(hctrl_, ctrl_.p, sizeof(Ctrl<real>), hipMemcpyDeviceToHost, stream));
-    wait_stream();
-}
-
-// host wait for the session stream; partitioned sessions wait under the
-// transport's watchdog (a stalled halo exchange fails the call with the
-// rank, peers, bytes and iteration instead of hanging)
-template <typename real>
-void QuadSession<real>::wait_stream() {
-    if (!halo_) { PFDR_HIP(hipStreamSynchronize(stream)); return; }
-    halo_->tr->phase = "iterations";
-    halo_->tr->iteration = it_;
-    halo_->tr->wait(stream);
 }
 
 // R = Y - A X (direct mode), gated
@@ -1731,38 +1601,29 @@ void QuadSession<real>::sweeps(const Ctrl<real> *c) {
     }
 }
 
-// iteration t = it0_ + 1 + i of a speculative session (see spec_)
+// the sweeps of speculative iteration t, on its buffers (b = t mod D)
 template <typename real>
-void QuadSession<real>::body_spec(int i, int n) {
-    hipStream_t s = stream;
-    const int t = it0_ + 1 + i;
-    const Ctrl<real> *c = ctrl_.p;
-    const int b = t % sd_;
-    if (i >= sd_) PFDR_HIP(hipStreamWaitEvent(s, evd_[b], 0));  // the decision on t - D
+void QuadSession<real>::spec_sweeps(int t, int b) {
     xr_ = xpb(t - 1);
     xw_ = xpb(t);
-    real *terms = terms_.p + (long)b * 2 * tstride_, *part = vpart_.p + (long)b * 2 * nbv_;
     real *const keep = terms_.p, *const keepp = vpart_.p;
-    terms_.p = terms;  // vargs() hands the sweep this iteration's terms
-    vpart_.p = part;
-    sweeps(c);
+    terms_.p += (long)b * 2 * tstride_;  // vargs() hands the sweep this iteration's terms
+    vpart_.p += (long)b * 2 * nbv_;
+    sweeps(ctrl_.p);
     terms_.p = keep;
     vpart_.p = keepp;
     xr_ = xw_ = xp_.p;
-    PFDR_HIP(hipEventRecord(evv_[b], s));
-    const hipStream_t es = evs();
-    PFDR_HIP(hipStreamWaitEvent(es, evv_[b], 0));
-    seq_evolution(terms, part, es);  // overlaps the sweeps of t + 1 (not when serial)
-    k_decide<real><<<1, 64, 0, es>>>(ctrl_.p, red_.p, rec_dif_ ? Dif_.p : nullptr, 1);
-    PFDR_HIP(hipGetLastError());
-    PFDR_HIP(hipEventRecord(evd_[b], es));
-    if (i == n - 1) PFDR_HIP(hipStreamWaitEvent(s, evd_[b], 0));  // join: the chunk's last
+}
+
+template <typename real>
+void QuadSession<real>::spec_decide(int b, hipStream_t s) {
+    seq_evolution(terms_.p + (long)b * 2 * tstride_, vpart_.p + (long)b * 2 * nbv_, s);
+    k_decide<real><<<1, 64, 0, s>>>(ctrl_.p, red_.p, rec_dif_ ? Dif_.p : nullptr, 1);
 }
 
 template <typename real>
 void QuadSession<real>::body(int i, int n) {
     hipStream_t s = stream;
-    if (spec_) { body_spec(i, n); return; }
     const bool gated = track_ || rec_obj_;
     const Ctrl<real> *c = gated ? ctrl_.p : nullptr;
     if (fuse_) {
@@ -1812,15 +1673,7 @@ void QuadSession<real>::body(int i, int n) {
 // from them when the terms lie in vertex order)
 template <typename real>
 void QuadSession<real>::seq_evolution(real *terms, const real *part, hipStream_t s) {
-    const int *halt = &ctrl_.p->halt;
-    if (!halo_) {
-        mono_sum<real>(V_, terms, nullptr, 0, nullptr, red_.p, nullptr, dws_.p, s, 2, tstride_,
-                       halt, reordered_ ? nullptr : part, nbv_);
-    } else if (!lab_.p) {
-        chain_.run(etr(), terms, tstride_, red_.p, halt, s);
-    } else {
-        route_.run(etr(), terms, tstride_, red_.p, halt, s);
-    }
+    evolution_sum(terms, V_, 2, tstride_, reordered_ ? nullptr : part, nbv_, s);
 }
 
 // interior edge range and vertex-block range of a partitioned session (the
@@ -1877,66 +1730,10 @@ void QuadSession<real>::plan_overlap() {
     (void)s;
 }
 
-// the captured graph of n bodies (a whole chunk, or a run's tail after
-// prepare()), instantiated once -- at the end of the setup for chunk_, and
-// again after a reconditioning dropped them
-template <typename real>
-hipGraphExec_t QuadSession<real>::chunk_graph(int n) {
-    const int key = kSpecMax * n + (spec_ ? it0_ % sd_ : 0);  // speculative: X buffers by t mod D
-    auto it = graphs_.find(key);
-    if (it != graphs_.end()) return it->second;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    PFDR_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    try {
-        for (int i = 0; i < n; i++) body(i, n);
-    } catch (...) {
-        (void)hipStreamEndCapture(stream, &g);
-        if (g) (void)hipGraphDestroy(g);
-        throw;
-    }
-    PFDR_HIP(hipStreamEndCapture(stream, &g));
-    const hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    PFDR_HIP(e);
-    // uploaded now, so that its first replay (a timed run's, after
-    // prepare()) pays no upload: the driver's 20-step line 0.522 -> 0.517 ms
-    PFDR_HIP(hipGraphUpload(ge, stream));
-    graphs_.emplace(key, ge);
-    return ge;
-}
-
-// whole chunks replay the captured graph; a partial chunk (the tail of a
-// run) replays one only if prepare() built it, else it is launched directly
-// rather than captured for one use
-template <typename real>
-void QuadSession<real>::run_bodies(int n) {
-    it0_ = it_;
-    const int key = kSpecMax * n + (spec_ ? it0_ % sd_ : 0);
-    if (!prof.on && capturable_ && graphs_.count(key)) {
-        PFDR_HIP(hipGraphLaunch(graphs_[key], stream));
-        return;
-    }
-    if (!graphs_ok_ || prof.on || n != chunk_) {
-        for (int i = 0; i < n; i++) body(i, n);
-        return;
-    }
-    PFDR_HIP(hipGraphLaunch(chunk_graph(chunk_), stream));
-}
-
-// the graphs a run of `iters` iterations will replay (chunks of chunk_ and
-// the tail), built now so that the run itself launches no capture
-template <typename real>
-void QuadSession<real>::prepare(int iters) {
-    if (!capturable_ || iters <= 0) return;
-    it0_ = it_;  // (the run starts here: its parity)
-    if (iters >= chunk_) (void)chunk_graph(chunk_);
-    if (iters % chunk_) (void)chunk_graph(iters % chunk_);
-    PFDR_HIP(hipStreamSynchronize(stream));
-}
-
+// rank 0 of a partition reports
 template <typename real>
 void QuadSession<real>::print_progress() {
+    hctrl_->it = it_;  // (an ungated run: the mirror is not read back)
     if (halo_ && halo_->tr->rank != 0) return;
     printf("iteration %d (max. %d)\n", it_, itMax_);
     if (track_) {
@@ -1947,108 +1744,13 @@ void QuadSession<real>::print_progress() {
 }
 
 template <typename real>
-int QuadSession<real>::run(int iters) {
-    const bool gated = track_ || rec_obj_;
-    const int target = (int)std::min<long>((long)it_ + std::max(iters, 0), (long)itMax_);
-    if (gated && !halo_ && !spec_) return run_pipelined(target);
-    // every rank runs the same number of bodies: the decisions come from
-    // all-reduced values, so the control blocks agree
-    while (!stopped_ && it_ < target) {
-        const int n = std::min(target - it_, chunk_);
-        if (tiny_) tiny_chunk(n);
-        else run_bodies(n);
-        if (gated) {
-            pull_ctrl();
-            it_ = hctrl_->it;
-            if (hctrl_->stop) {
-                stopped_ = true;
-            } else if (hctrl_->recond) {
-                if (verbose_) { print_progress(); printf("Reconditioning... "); fflush(stdout); }
-                precondition(false);
-                refresh_ends();  // (X, P) and (Ga, 1/Aux) rewritten
-                drop_graphs();  // A1_ now holds the splitting weights' factors
-                difRcd2_ *= real(0.01);  // ref :458
-                hctrl_->difRcd = difRcd2_;
-                hctrl_->recond = 0;
-                hctrl_->halt = 0;
-                push_ctrl();
-                if (verbose_) { printf("done.\n"); fflush(stdout); }
-            }
-        } else {
-            it_ += n;
-            if (it_ >= itMax_) stopped_ = true;
-        }
-        if (verbose_ && (it_ >= next_print_ || stopped_)) {
-            if (!gated) hctrl_->it = it_;
-            print_progress();
-            next_print_ = it_ + verbose_;
-        }
-    }
-    wait_stream();
-    if (prof.on) prof.resolve();
-    return it_;
-}
-
-// Gated single-GPU runs: chunk k + 1 is launched before the host reads the
-// control block chunk k left (a device-to-host snapshot ordered between the
-// two chunks), so the host's round trip -- ≈35-45 us per chunk, a tenth of
-// a 32-iteration chunk of C1 -- overlaps the GPU's work instead of idling
-// it.  A chunk launched after a stop or a reconditioning request runs with
-// the halt flag set: every kernel of it returns at once and changes nothing,
-// so the iterates, the iteration count and Dif are those of the one-chunk-
-// at-a-time loop.
-template <typename real>
-int QuadSession<real>::run_pipelined(int target) {
-    for (int k = 0; k < 2; k++) {
-        if (!snap_[k]) snap_[k] = static_cast<Ctrl<real> *>(pinned_small_get());
-        if (!snapev_[k]) PFDR_HIP(hipEventCreateWithFlags(&snapev_[k], hipEventDisableTiming));
-    }
-    int k = 0, nq = 0;  // slot of the oldest unread snapshot, chunks in flight
-    int ahead = it_;    // iterations launched so far, if none stops
-    while (!stopped_) {
-        while (nq < 2 && ahead < target) {
-            const int n = std::min(target - ahead, chunk_);
-            if (tiny_) tiny_chunk(n);
-            else run_bodies(n);
-            const int slot = (k + nq) & 1;
-            PFDR_HIP(hipMemcpyAsync(snap_[slot], ctrl_.p, sizeof(Ctrl<real>),
-                                    hipMemcpyDeviceToHost, stream));
-            PFDR_HIP(hipEventRecord(snapev_[slot], stream));
-            ahead += n;
-            nq++;
-        }
-        if (nq == 0) break;
-        PFDR_HIP(hipEventSynchronize(snapev_[k]));
-        *hctrl_ = *snap_[k];
-        k ^= 1;
-        nq--;
-        it_ = hctrl_->it;
-        if (hctrl_->stop) {
-            stopped_ = true;
-        } else if (hctrl_->recond) {
-            wait_stream();  // the chunk queued behind it ran halted
-            nq = 0;
-            ahead = it_;
-            if (verbose_) { print_progress(); printf("Reconditioning... "); fflush(stdout); }
-            precondition(false);
-            refresh_ends();
-            drop_graphs();
-            difRcd2_ *= real(0.01);  // ref :458
-            hctrl_->difRcd = difRcd2_;
-            hctrl_->recond = 0;
-            hctrl_->halt = 0;
-            push_ctrl();
-            if (verbose_) { printf("done.\n"); fflush(stdout); }
-        }
-        if (verbose_ && (it_ >= next_print_ || stopped_)) {
-            print_progress();
-            next_print_ = it_ + verbose_;
-        }
-        if (!stopped_ && nq == 0 && ahead >= target) break;
-    }
-    wait_stream();
-    if (prof.on) prof.resolve();
-    return it_;
+void QuadSession<real>::recondition() {
+    if (verbose_) { print_progress(); printf("Reconditioning... "); fflush(stdout); }
+    precondition(false);
+    refresh_ends();  // (X, P) and (Ga, 1/Aux) rewritten
+    drop_graphs();  // A1_ now holds the splitting weights' factors
+    difRcd2_ *= real(0.01);  // ref :458
+    hctrl_->difRcd = difRcd2_;
 }
 
 template <typename real>
@@ -2072,11 +1774,7 @@ void QuadSession<real>::result(void *X_host, int *it, void *Obj_host, void *Dif_
         void *dx = device_x();
         hp.copy(X_host, dx, sizeof(real) * V_, hipMemcpyDeviceToHost);
     }
-    if (it) *it = it_;
-    if (Obj_host && rec_obj_)
-        hp.copy(Obj_host, Obj_.p, sizeof(real) * (it_ + 1), hipMemcpyDeviceToHost);
-    if (Dif_host && rec_dif_ && it_ > 0)
-        hp.copy(Dif_host, Dif_.p, sizeof(real) * it_, hipMemcpyDeviceToHost);
+    this->download_records(it, Obj_host, Dif_host, Obj_.p, Dif_.p, hp);
     hp.release();
     PFDR_HIP(hipStreamSynchronize(s));
 }
@@ -2113,37 +1811,7 @@ static int quadratic_host(const char *fn, int kind, int V, int E, int N, real *X
     p.min = mn; p.max = mx; p.Ltype = Ltype; p.L = L;
     p.rho = rho; p.condMin = condMin; p.difRcd = difRcd; p.difTol = difTol;
     p.itMax = itMax; p.verbose = verbose;
-    p.record_obj = Obj != nullptr;
-    p.record_dif = Dif != nullptr;
-    try {
-        CallTrace tr(fn);
-        if (verbose) { printf("Initializing constants and variables... "); fflush(stdout); }
-        // (a sparse A stays on one GPU whatever the device group)
-        const std::vector<int> devs = csc ? std::vector<int>() : multidev_devices(&p);
-        if (!devs.empty()) {  // partitioned across the configured devices
-            if (verbose) { printf("done (%d devices).\n", (int)devs.size()); fflush(stdout); }
-            int its = 0;
-            multidev_solve(&p, devs, &its, Obj, Dif);
-            if (it) *it = its;
-            tr.finish(V, E, N, 1, its);
-            return PFDR_OK;
-        }
-        std::unique_ptr<QuadSession<real>> s(new QuadSession<real>(&p, csc));
-        if (verbose) { printf("done.\nPreconditioned forward-Douglas-Rachford algorithm\n"); fflush(stdout); }
-        tr.setup_done();
-        s->run(itMax);
-        tr.run_done();
-        int its = 0;
-        s->result(X, &its, Obj, Dif);
-        if (it) *it = its;
-        s.reset();
-        tr.finish(V, E, N, 1, its);
-    } catch (const HipError &h) {
-        return report_error(fn, h);
-    } catch (const std::exception &ex) {
-        return report_error(fn, ex.what());
-    }
-    return PFDR_OK;
+    return solve_one_call<QuadSession<real>>(fn, p, X, it, Obj, Dif, N, 1, !csc, csc);
 }
 
 }  // namespace pfdr

@@ -29,10 +29,8 @@
 #include <memory>
 
 #include "pfdr_graph.hpp"
-#include "pfdr_halo.hpp"
-#include "pfdr_monosum.hpp"
+#include "pfdr_loop.hpp"
 #include "pfdr_proj.hpp"
-#include "pfdr_session.hpp"
 #include "pfdr_sort.hpp"
 
 namespace pfdr {
@@ -2147,7 +2145,9 @@ __global__ void k_sxt_rec(int nb, int V, int vb, int K, int cap, const int *__re
     atomicAdd(nok, 1);
 }
 
-// *bad += the entries of La_d1 that differ from La_d1[0]
+// *bad += the entries of La_d1 that differ from La_d1[0].  (The session's
+// own kernel: the quadratic file's k_uniform_check, launched from here, made
+// the runtime load that file's code object, which cost C4 1 %)
 template <typename real>
 __global__ void k_sx_uniform_check(long E, const real *__restrict__ x, int *__restrict__ bad) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2167,17 +2167,6 @@ template <typename real>
 __global__ void k_sx_p_from_pf(long n, const SxR2<real> *__restrict__ PF, real *__restrict__ P) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) P[i] = PF[i].x;
-}
-
-template <typename real>
-static void sx_copy_in(DevBuf<real> &d, const void *src, size_t n, int mem, hipStream_t s,
-                       HostPins &pins) {
-    if (!src || !n) { d.release(); return; }
-    d.alloc(n);
-    if (mem == PFDR_MEM_DEVICE)
-        PFDR_HIP(hipMemcpyAsync(d.p, src, n * sizeof(real), hipMemcpyDeviceToDevice, s));
-    else
-        pins.copy(d.p, src, n * sizeof(real), hipMemcpyHostToDevice);
 }
 
 // proj_simplex_metric: a segment of G = 4..64 lanes per column with J
@@ -2204,42 +2193,29 @@ static void launch_proj(real *X, const real *M, int D, int N, int nm, const real
 }
 
 template <typename real>
-class SimplexSession final : public SessionBase {
+class SimplexSession final : public IterLoop<real> {
   public:
     explicit SimplexSession(const pfdr_problem *p);
-    ~SimplexSession() override {
-        if (hctrl_) {
-            (void)hipStreamSynchronize(stream);  // no control-block copy in flight
-            pinned_small_put(hctrl_);
-        }
-        for (Ctrl<real> *c : snap_) if (c) pinned_small_put(c);
-        for (hipEvent_t e : snapev_) if (e) (void)hipEventDestroy(e);
-        drop_graphs();
-        for (hipEvent_t e : evv_) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : evd_) if (e) (void)hipEventDestroy(e);
-        if (evs_) {
-            (void)hipStreamSynchronize(evs_);
-            (void)hipStreamDestroy(evs_);
-        }
-    }
-    int run(int iters) override;
+    ~SimplexSession() override { this->close(); }  // (streams drained before any buffer goes)
     void result(void *X_host, int *it, void *Obj_host, void *Dif_host) override;
     void *device_x() override {
         sync_p(it_);
         PFDR_HIP(hipStreamSynchronize(stream));
         return Pb(it_);
     }
-    void on_stop_or_recond();
 
   private:
+    using L = IterLoop<real>;
+    using L::stream, L::prof, L::device, L::device_bytes, L::ghosts, L::tiled_blocks, L::tiny;
+    using L::record_blocks, L::la_uniform, L::seqdif;
+    using L::halo_, L::ctrl_, L::hctrl_, L::itMax_, L::verbose_, L::it_, L::stopped_, L::chunk_;
+    using L::tiny_, L::graphs_ok_, L::capturable_, L::kSpecMax, L::spec_, L::sd_, L::seqdif_;
+    using L::chain_, L::route_, L::dws_, L::red_, L::push_ctrl, L::drop_graphs;
     SxConst<real> c_;
-    int V_, K_, itMax_, verbose_;
+    int V_, K_;
     int Vg_;        // owned + ghost vertices (distributed)
     long Vglob_;    // vertices over all ranks
     long E_, EK_, VK_, R_ = 0;
-    std::unique_ptr<Halo> halo_;  // vertex partition (null on one GPU)
-    void wait_stream();
-    DevBuf<real> red_;            // all-reduced scalars
     real rho_, condMin_, difTol_, difRcd_, cap_;
     bool rec_obj_, rec_dif_;
     int track_;  // 0, 1 (l1 evolution), 2 (labels)
@@ -2247,46 +2223,23 @@ class SimplexSession final : public SessionBase {
     // include/pfdr_mi355x.h): the vertex sweep stores the terms in the
     // reference's order (v K + k, or v for label changes), one binade-scan sum
     // (mono_sum) replaces the block partials' tree
-    bool seqdif_ = false;
+    // (partitions: label counts (track 2) add 0 / 1, exact in any order, so
+    // they keep the tree)
     long nterms_ = 0;
     DevBuf<real> terms_;
-    DevBuf<char> dws_;
     static constexpr long kSeqDifMin = 1L << 17;  // AUTO: sums of at least this many terms
-    // partitions: the ranks' terms summed rank to rank in the caller's order
-    // (ChainSum); a relabelled partition (vtx_label) first routes each
-    // vertex's K terms to the rank whose caller-order slice holds its label
-    // (TermRoute), then chains.  Label counts (track 2) add 0 / 1: exact in
-    // any order, so partitions keep the tree for them.
-    ChainSum<real> chain_;
-    TermRoute<real> route_;
-    // the evolution sums' transport: a speculative partition's own split one
-    // (beside the next iteration's exchanges, QuadSession::evtr_)
-    std::unique_ptr<Transport> evtr_;
-    Transport &etr() { return evtr_ ? *evtr_ : *halo_->tr; }
-    void seq_evolution(real *terms, hipStream_t s);
-    // Speculative iteration (sequential evolution, difRcd = 0, no objective
-    // record; one GPU or a partition), as the quadratic session's spec_: the
-    // sum and the decision on iteration t run on evs_ beside the sweeps of
-    // t + 1 ... t + D - 1 (depth D = sd_: 2, or 4 on three or more ranks), P
-    // and (P, step) cycle through D buffers (iteration t reads Pb(t - 1),
-    // writes Pb(t)), the terms through D; a stop at t leaves P_t in Pb(t) and
-    // the speculative iterations after it are discarded.
-    static constexpr int kSpecMax = 4;
-    bool spec_ = false;
-    int sd_ = 2;
-    int it0_ = 0;
+    void seq_evolution(real *terms, hipStream_t s) {
+        this->evolution_sum(terms, nterms_, 1, 0, nullptr, 0, s);
+    }
+    // Speculative iteration (IterLoop::spec_; here: difRcd = 0): P and
+    // (P, step) cycle through D buffers (iteration t reads Pb(t - 1), writes
+    // Pb(t)), the terms through D
     DevBuf<real> Px_[kSpecMax - 1];           // P buffers 1 .. D - 1 (0 is P_)
     DevBuf<SxR2<real>> PFx_[kSpecMax - 1];    // (P, step) likewise
     real *Pb(int t) { return spec_ && t % sd_ ? Px_[t % sd_ - 1].p : P_.p; }
     SxR2<real> *PFb(int t) { return spec_ && t % sd_ ? PFx_[t % sd_ - 1].p : PF_.p; }
-    hipStream_t evs_ = nullptr;  // the decisions' stream (null: PFDR_SPEC_SERIAL, the session's)
-    hipStream_t evs() const { return evs_ ? evs_ : stream; }
-    hipEvent_t evv_[kSpecMax] = {}, evd_[kSpecMax] = {};
-    // pipelined gated runs (QuadSession::run_pipelined): control-block
-    // snapshots of two chunks in flight
-    Ctrl<real> *snap_[2] = {};
-    hipEvent_t snapev_[2] = {};
-    void body_spec(int i, int n);
+    void spec_sweeps(int t, int b) override;
+    void spec_decide(int b, hipStream_t s) override;
     void sweeps(const Ctrl<real> *c, int t);  // edge + vertex pass of iteration t
     DevBuf<int> Eu_, Ev_;
     DevBuf<real> La_d1_, La_f_, Q_, P_, Pavg_, Ga_, GaQ_, invAux_, lab_;
@@ -2303,8 +2256,6 @@ class SimplexSession final : public SessionBase {
     // the factors (C4: 1.076 -> 0.950 ms, r1zw; odd K stored: 1.24 vs 1.30 ms)
     DevBuf<real> Wd1u_, Wd1v_, Th_;
     bool sx_pw_ = true;
-    DevBuf<Ctrl<real>> ctrl_;
-    Ctrl<real> *hctrl_ = nullptr;
     Incidence inc_;
     HostPins pins_;  // caller arrays pinned for the setup copies
     int nbv_, nbe_;
@@ -2358,34 +2309,16 @@ class SimplexSession final : public SessionBase {
     // XCD-aware block order: runs of 64 edge blocks per XCD (C4 edge sweep
     // 1.275 -> 1.244 ms, r1zm); the vertex sweep in plain order
     static constexpr int sx_xcd_e_ = 64, sx_xcd_v_ = 0;
-    int it_ = 0;
-    bool stopped_ = false;
-    int chunk_ = 32;
-    int next_print_ = 0;
-    // hipGraph of a chunk of bodies (single GPU, no objective record,
-    // unprofiled; re-captured after a reconditioning): small problems --
-    // cut pursuit's reduced ones -- are otherwise bound by the host's three
-    // launches per iteration.
-    bool graphs_ok_ = false;
-    std::map<int, hipGraphExec_t> graphs_;
-    void run_bodies(int n);
-    bool capturable_ = false;  // prepare(): graphs of any run length on request
-  public:
-    void prepare(int iters) override;
-  private:
     // small single-GPU problems: a chunk of iterations in one workgroup
     // (k_sx_tiny_iterate; PFDR_SX_TINY = most (edge, label) entries, 0 off)
-    bool tiny_ = false;
-    void tiny_chunk(int n);
-    hipGraphExec_t chunk_graph(int n);
-    void drop_graphs() {
-        for (auto &kv : graphs_) (void)hipGraphExecDestroy(kv.second);
-        graphs_.clear();
-    }
+    void tiny_chunk(int n) override;
 
     void precondition(bool init);
     void objective();
-    void body();
+    void body(int i, int n) override;
+    void recondition() override;
+    void print_progress() override;
+    bool gated() const override { return track_ || rec_obj_; }
     // K-wide ghost rows of a [Vg][K] array from their owners
     void pullK(DevBuf<real> &b) {
         if (halo_) halo_->pull(b.p, K_ * (int)sizeof(real), stream);
@@ -2531,7 +2464,7 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
     contribution_incidence(Eu_.p, Ev_.p, E_, V_, sxtile_ ? perm.p : eg.p, e_offset, halo_.get(),
                            inc_, s);
     const size_t VgK = (size_t)Vg_ * K_;
-    sx_copy_in(La_d1_, p->La_d1, E_, mem, s, pins_);
+    copy_in(La_d1_, p->La_d1, E_, mem, s, pins_);
     if (sxtile_) {
         DevBuf<real> t(E_);
         k_sx_permute<real><<<grid_for(E_), kBlock, 0, s>>>(E_, perm.p, La_d1_.p, t.p);
@@ -2551,7 +2484,7 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
         la_u_ = h == 0;
         la_uniform = la_u_ ? 1 : 0;
     }
-    if (c_.loss != LOSS_LINEAR) sx_copy_in(La_f_, p->La_l1, V_, mem, s, pins_);
+    if (c_.loss != LOSS_LINEAR) copy_in(La_f_, p->La_l1, V_, mem, s, pins_);
     for (auto q : {std::make_pair(&Q_, p->Y), std::make_pair(&P_, (const void *)p->X)}) {
         q.first->alloc(VgK);  // owned rows, then the ghosts' from their owners
         if (kind == hipMemcpyHostToDevice) pins_.copy(q.first->p, q.second, VK_ * sizeof(real), kind);
@@ -2601,16 +2534,11 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
         k_sx_labels<real><<<nbv_, kBlock, 0, s>>>(V_, K_, P_.p, lab_.p);
     }
 
-    ctrl_.alloc(1);
-    static_assert(sizeof(Ctrl<real>) <= kPinnedSmall, "control block");
-    hctrl_ = static_cast<Ctrl<real> *>(pinned_small_get());
-    std::memset(hctrl_, 0, sizeof(Ctrl<real>));
-    hctrl_->obj_it = -1;
-    hctrl_->itMax = itMax_;
+    this->alloc_ctrl();
     hctrl_->dif = difTol_ > difRcd_ ? difTol_ : difRcd_;  // ref :445
     hctrl_->difTol = difTol_;
     hctrl_->difRcd = difRcd_;
-    PFDR_HIP(hipMemcpyAsync(ctrl_.p, hctrl_, sizeof(Ctrl<real>), hipMemcpyHostToDevice, s));
+    push_ctrl();
 
     if (EK_) k_sx_z_init<real><<<grid_for(EK_), kBlock, 0, s>>>(EK_, K_, Eu_.p, Ev_.p, P_.p, Zu_.p, zv_);
     precondition(true);
@@ -2669,11 +2597,9 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
         }
         seqdif = 1;
         const int smode = spec_mode(p);
-        const bool serial = smode == PFDR_SPEC_SERIAL;
         spec_ = difRcd_ == real(0) && !rec_obj_ && smode != PFDR_SPEC_OFF;
-        if (spec_ && halo_ && !serial) evtr_ = halo_->tr->split(s);  // (collective: every rank alike)
         if (spec_) {
-            sd_ = halo_ && halo_->tr->nranks >= 3 ? 4 : 2;
+            this->spec_setup(smode == PFDR_SPEC_SERIAL);
             DevBuf<real> t2((size_t)sd_ * n);  // terms of D iterations
             std::swap(terms_.p, t2.p);
             std::swap(terms_.n, t2.n);
@@ -2681,26 +2607,10 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
                 Px_[k].alloc((size_t)Vg_ * K_);
                 PFx_[k].alloc((size_t)Vg_ * K_);
             }
-            if (!serial) PFDR_HIP(hipStreamCreateWithFlags(&evs_, hipStreamNonBlocking));
-            for (int k = 0; k < sd_; k++) {
-                PFDR_HIP(hipEventCreateWithFlags(&evv_[k], hipEventDisableTiming));
-                PFDR_HIP(hipEventCreateWithFlags(&evd_[k], hipEventDisableTiming));
-            }
-            speculative = serial ? 2 : 1;
-            graphs_ok_ = capturable_ = false;  // launched directly (see QuadSession)
         }
     }
     if (vb_ && !tiny_ && !halo_) fused_sweep_setup();
-    if (graphs_ok_) {  // instantiated with the setup
-        try {
-            (void)chunk_graph(chunk_);
-        } catch (const std::exception &) {
-            if (!halo_) throw;
-            graphs_ok_ = capturable_ = false;  // this transport would not capture: launch directly
-            (void)hipGetLastError();
-        }
-    }
-    graphs = graphs_ok_ ? 1 : 0;
+    this->instantiate_setup_graph();
     device_bytes = (int64_t)(Eu_.n + Ev_.n + inc_.ptr.n + inc_.idx.n) * 4;
     for (DevBuf<real> *b : {&La_d1_, &La_f_, &Q_, &P_, &Pavg_, &Ga_, &GaQ_, &invAux_, &lab_,
                             &Zu_, &A1_, &Wd1u_, &Wd1v_, &Th_, &wz_, &part_, &opart_, &Obj_,
@@ -2789,7 +2699,7 @@ void SimplexSession<real>::objective() {
                                                  c_.loss == LOSS_QUAD, ctrl_.p, Obj_.p,
                                                  halo_ ? red_.p : nullptr);
     if (halo_) {
-        halo_->tr->allreduce_sum(red_.p, 2, sizeof(real) == 4 ? PFDR_F32 : PFDR_F64, s);
+        halo_->tr->allreduce_sum(red_.p, 2, dtype_of<real>(), s);
         k_sx_obj_write<real><<<1, 1, 0, s>>>(red_.p, c_.loss == LOSS_QUAD, ctrl_.p, Obj_.p);
     }
     PFDR_HIP(hipGetLastError());
@@ -2862,31 +2772,24 @@ void SimplexSession<real>::sync_p(int t) {
     PFDR_HIP(hipGetLastError());
 }
 
-// iteration t = it0_ + 1 + i of a speculative session (see spec_)
+// the sweeps of speculative iteration t, on its terms (b = t mod D)
 template <typename real>
-void SimplexSession<real>::body_spec(int i, int n) {
-    hipStream_t s = stream;
-    const int t = it0_ + 1 + i;
-    const int b = t % sd_;
-    if (i >= sd_) PFDR_HIP(hipStreamWaitEvent(s, evd_[b], 0));  // the decision on t - D
-    real *terms = terms_.p + (long)b * (terms_.n / sd_);
+void SimplexSession<real>::spec_sweeps(int t, int b) {
     real *const keep = terms_.p;
-    terms_.p = terms;
+    terms_.p += (long)b * (terms_.n / sd_);
     sweeps(ctrl_.p, t);
     terms_.p = keep;
-    PFDR_HIP(hipEventRecord(evv_[b], s));
-    const hipStream_t es = evs();
-    PFDR_HIP(hipStreamWaitEvent(es, evv_[b], 0));
-    seq_evolution(terms, es);  // overlaps the sweeps of t + 1 (not when serial)
-    k_sx_finalize<real><<<1, kBlock, 0, es>>>(0, nullptr, Vglob_, track_, ctrl_.p,
-                                                rec_dif_ ? Dif_.p : nullptr, red_.p);
-    PFDR_HIP(hipGetLastError());
-    PFDR_HIP(hipEventRecord(evd_[b], es));
-    if (i == n - 1) PFDR_HIP(hipStreamWaitEvent(s, evd_[b], 0));  // join: the chunk's last
 }
 
 template <typename real>
-void SimplexSession<real>::body() {
+void SimplexSession<real>::spec_decide(int b, hipStream_t s) {
+    seq_evolution(terms_.p + (long)b * (terms_.n / sd_), s);
+    k_sx_finalize<real><<<1, kBlock, 0, s>>>(0, nullptr, Vglob_, track_, ctrl_.p,
+                                               rec_dif_ ? Dif_.p : nullptr, red_.p);
+}
+
+template <typename real>
+void SimplexSession<real>::body(int, int) {
     hipStream_t s = stream;
     const bool gated = track_ || rec_obj_;
     const Ctrl<real> *c = gated ? ctrl_.p : nullptr;
@@ -2902,7 +2805,7 @@ void SimplexSession<real>::body() {
     } else if (gated && halo_) {
         if (track_) {
             k_sx_partsum<real><<<1, kBlock, 0, s>>>(nparts, part_.p, ctrl_.p, red_.p);
-            halo_->tr->allreduce_sum(red_.p, 1, sizeof(real) == 4 ? PFDR_F32 : PFDR_F64, s);
+            halo_->tr->allreduce_sum(red_.p, 1, dtype_of<real>(), s);
         }
         k_sx_finalize<real><<<1, kBlock, 0, s>>>(0, nullptr, Vglob_, track_, ctrl_.p,
                                                  rec_dif_ ? Dif_.p : nullptr, red_.p);
@@ -2998,21 +2901,6 @@ void SimplexSession<real>::sweeps(const Ctrl<real> *c, int t) {
     PFDR_HIP(hipGetLastError());
 }
 
-// red_[0] = the evolution sum over every (vertex, label) in the caller's
-// order, rounded as the reference's one-thread loop
-template <typename real>
-void SimplexSession<real>::seq_evolution(real *terms, hipStream_t s) {
-    const int *halt = &ctrl_.p->halt;
-    if (!halo_) {
-        mono_sum<real>(nterms_, terms, nullptr, 0, nullptr, red_.p, nullptr, dws_.p, s, 1, 0,
-                       halt);
-    } else if (!route_.ready()) {
-        chain_.run(etr(), terms, 0, red_.p, halt, s);
-    } else {
-        route_.run(etr(), terms, 0, red_.p, halt, s);
-    }
-}
-
 // K-wide DR contributions of ghost-vertex ends to their owners
 template <typename real>
 void SimplexSession<real>::push_wz() {
@@ -3051,167 +2939,30 @@ void SimplexSession<real>::tiny_chunk(int n) {
     PFDR_HIP(hipGetLastError());
 }
 
-// the captured graph of a whole chunk (chunk_ bodies), instantiated once --
-// at the end of the setup, and again after a reconditioning dropped it
 template <typename real>
-hipGraphExec_t SimplexSession<real>::chunk_graph(int n) {
-    const int key = kSpecMax * n + (spec_ ? it0_ % sd_ : 0);  // speculative: P buffers by t mod D
-    auto it = graphs_.find(key);
-    if (it != graphs_.end()) return it->second;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    PFDR_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    try {
-        for (int i = 0; i < n; i++) spec_ ? body_spec(i, n) : body();
-    } catch (...) {
-        (void)hipStreamEndCapture(stream, &g);
-        if (g) (void)hipGraphDestroy(g);
-        throw;
-    }
-    PFDR_HIP(hipStreamEndCapture(stream, &g));
-    const hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    PFDR_HIP(e);
-    // uploaded now, so that its first replay (a timed run's, after
-    // prepare()) pays no upload: the driver's 20-step line 0.522 -> 0.517 ms
-    PFDR_HIP(hipGraphUpload(ge, stream));
-    graphs_.emplace(key, ge);
-    return ge;
+void SimplexSession<real>::recondition() {
+    if (verbose_) { printf("Reconditioning... "); fflush(stdout); }
+    sync_p(it_);
+    precondition(false);
+    drop_graphs();  // kernel arguments (A1_, stored weights) may have changed
+    k_sx_explicit<real><<<grid_for(VK_), kBlock, 0, stream>>>(VK_, c_, P_.p, GaQ_.p, Q_.p, PF_.p);
+    PFDR_HIP(hipGetLastError());
+    pullPF();
+    difRcd_ *= real(0.1);  // ref :563
+    hctrl_->difRcd = difRcd_;
 }
 
+// every rank of a partition reports
 template <typename real>
-void SimplexSession<real>::run_bodies(int n) {
-    it0_ = it_;
-    const int key = kSpecMax * n + (spec_ ? it0_ % sd_ : 0);
-    if (!prof.on && capturable_ && graphs_.count(key)) {  // prepared (or whole) chunk
-        PFDR_HIP(hipGraphLaunch(graphs_[key], stream));
-        return;
-    }
-    if (!graphs_ok_ || prof.on || n != chunk_) {
-        for (int i = 0; i < n; i++) spec_ ? body_spec(i, n) : body();
-        return;
-    }
-    PFDR_HIP(hipGraphLaunch(chunk_graph(chunk_), stream));
-}
-
-// the graphs a run of `iters` iterations will replay, built now
-template <typename real>
-void SimplexSession<real>::prepare(int iters) {
-    if (!capturable_ || iters <= 0) return;
-    it0_ = it_;
-    if (iters >= chunk_) (void)chunk_graph(chunk_);
-    if (iters % chunk_) (void)chunk_graph(iters % chunk_);
-    PFDR_HIP(hipStreamSynchronize(stream));
-}
-
-template <typename real>
-int SimplexSession<real>::run(int iters) {
-    const bool gated = track_ || rec_obj_;
-    const int target = (int)std::min<long>((long)it_ + std::max(iters, 0), (long)itMax_);
-    if (gated && !halo_ && !spec_) {
-        // two chunks in flight, as QuadSession::run_pipelined: chunk k + 1 is
-        // launched before the host reads chunk k's control-block snapshot; a
-        // chunk launched after a stop or a reconditioning request runs
-        // halted (every kernel returns at once)
-        for (int k = 0; k < 2; k++) {
-            if (!snap_[k]) snap_[k] = static_cast<Ctrl<real> *>(pinned_small_get());
-            if (!snapev_[k]) PFDR_HIP(hipEventCreateWithFlags(&snapev_[k], hipEventDisableTiming));
-        }
-        int k = 0, nq = 0, ahead = it_;
-        while (!stopped_) {
-            while (nq < 2 && ahead < target) {
-                const int n = std::min(target - ahead, chunk_);
-                if (tiny_) tiny_chunk(n);
-                else run_bodies(n);
-                const int slot = (k + nq) & 1;
-                PFDR_HIP(hipMemcpyAsync(snap_[slot], ctrl_.p, sizeof(Ctrl<real>),
-                                        hipMemcpyDeviceToHost, stream));
-                PFDR_HIP(hipEventRecord(snapev_[slot], stream));
-                ahead += n;
-                nq++;
-            }
-            if (nq == 0) break;
-            PFDR_HIP(hipEventSynchronize(snapev_[k]));
-            *hctrl_ = *snap_[k];
-            k ^= 1;
-            nq--;
-            it_ = hctrl_->it;
-            if (hctrl_->recond && !hctrl_->stop) {
-                wait_stream();  // the chunk queued behind it ran halted
-                nq = 0;
-                ahead = it_;
-            }
-            on_stop_or_recond();
-            if (!stopped_ && nq == 0 && ahead >= target) break;
-        }
-        wait_stream();
-        if (prof.on) prof.resolve();
-        return it_;
-    }
-    while (!stopped_ && it_ < target) {
-        const int n = std::min(target - it_, chunk_);
-        if (tiny_) tiny_chunk(n);
-        else run_bodies(n);
-        if (gated) {
-            PFDR_HIP(hipMemcpyAsync(hctrl_, ctrl_.p, sizeof(Ctrl<real>), hipMemcpyDeviceToHost, stream));
-            wait_stream();
-            it_ = hctrl_->it;
-            on_stop_or_recond();
-        } else {
-            it_ += n;
-            if (it_ >= itMax_) stopped_ = true;
-            on_stop_or_recond();
-        }
-    }
-    wait_stream();
-    if (prof.on) prof.resolve();
-    return it_;
-}
-
-// after a chunk: the stop or reconditioning the control block (hctrl_, just
-// read) asks for, then the progress line
-template <typename real>
-void SimplexSession<real>::on_stop_or_recond() {
-    const bool gated = track_ || rec_obj_;
-    if (gated) {
-        if (hctrl_->stop) {
-            stopped_ = true;
-        } else if (hctrl_->recond) {
-            if (verbose_) { printf("Reconditioning... "); fflush(stdout); }
-            sync_p(it_);
-            precondition(false);
-            drop_graphs();  // kernel arguments (A1_, stored weights) may have changed
-            k_sx_explicit<real><<<grid_for(VK_), kBlock, 0, stream>>>(VK_, c_, P_.p, GaQ_.p, Q_.p, PF_.p);
-            PFDR_HIP(hipGetLastError());
-            pullPF();
-            difRcd_ *= real(0.1);  // ref :563
-            hctrl_->difRcd = difRcd_;
-            hctrl_->recond = 0;
-            hctrl_->halt = 0;
-            PFDR_HIP(hipMemcpyAsync(ctrl_.p, hctrl_, sizeof(Ctrl<real>), hipMemcpyHostToDevice, stream));
-            if (verbose_) { printf("done.\n"); fflush(stdout); }
-        }
-    }
-    if (verbose_ && (it_ >= next_print_ || stopped_)) {
-        printf("iteration %d (max. %d)\n", it_, itMax_);
-        if (track_ == 2)
-            printf("label evolution %d (recond. %d; tol. %d)\n", (int)hctrl_->dif,
-                   (int)hctrl_->difRcd, (int)difTol_);
-        else if (track_ == 1)
-            printf("iterate evolution %g (recond. %g; tol. %g)\n", (double)hctrl_->dif,
-                   (double)hctrl_->difRcd, (double)difTol_);
-        fflush(stdout);
-        next_print_ = it_ + verbose_;
-    }
-}
-
-// host wait for the session stream (partitioned: under the transport's watchdog)
-template <typename real>
-void SimplexSession<real>::wait_stream() {
-    if (!halo_) { PFDR_HIP(hipStreamSynchronize(stream)); return; }
-    halo_->tr->phase = "iterations";
-    halo_->tr->iteration = it_;
-    halo_->tr->wait(stream);
+void SimplexSession<real>::print_progress() {
+    printf("iteration %d (max. %d)\n", it_, itMax_);
+    if (track_ == 2)
+        printf("label evolution %d (recond. %d; tol. %d)\n", (int)hctrl_->dif,
+               (int)hctrl_->difRcd, (int)difTol_);
+    else if (track_ == 1)
+        printf("iterate evolution %g (recond. %g; tol. %g)\n", (double)hctrl_->dif,
+               (double)hctrl_->difRcd, (double)difTol_);
+    fflush(stdout);
 }
 
 template <typename real>
@@ -3222,11 +2973,7 @@ void SimplexSession<real>::result(void *X_host, int *it, void *Obj_host, void *D
         sync_p(it_);
         hp.copy(X_host, Pb(it_), sizeof(real) * VK_, hipMemcpyDeviceToHost);
     }
-    if (it) *it = it_;
-    if (Obj_host && rec_obj_)
-        hp.copy(Obj_host, Obj_.p, sizeof(real) * (it_ + 1), hipMemcpyDeviceToHost);
-    if (Dif_host && rec_dif_ && it_ > 0)
-        hp.copy(Dif_host, Dif_.p, sizeof(real) * it_, hipMemcpyDeviceToHost);
+    this->download_records(it, Obj_host, Dif_host, Obj_.p, Dif_.p, hp);
     hp.release();
     PFDR_HIP(hipStreamSynchronize(s));
 }
@@ -3244,42 +2991,13 @@ static int simplex_host(const char *fn, int K, int V, int E, real al, const real
                         real *Dif, int verbose) {
     pfdr_problem p{};
     p.kind = PFDR_KIND_SIMPLEX;
-    p.dtype = sizeof(real) == 4 ? PFDR_F32 : PFDR_F64;
+    p.dtype = dtype_of<real>();
     p.mem = PFDR_MEM_HOST;
     p.V = V; p.E = E; p.K = K; p.al = al;
     p.X = P; p.Y = Q; p.Eu = Eu; p.Ev = Ev; p.La_d1 = La_d1; p.La_l1 = La_f;
     p.rho = rho; p.condMin = condMin; p.difRcd = difRcd; p.difTol = difTol;
     p.itMax = itMax; p.verbose = verbose;
-    p.record_obj = Obj != nullptr;
-    p.record_dif = Dif != nullptr;
-    try {
-        CallTrace tr(fn);
-        if (verbose) { printf("Initializing constants and variables... "); fflush(stdout); }
-        const std::vector<int> devs = multidev_devices(&p);
-        if (!devs.empty()) {  // partitioned across the configured devices
-            if (verbose) { printf("done (%d devices).\n", (int)devs.size()); fflush(stdout); }
-            int its = 0;
-            multidev_solve(&p, devs, &its, Obj, Dif);
-            if (it) *it = its;
-            tr.finish(V, E, 0, K, its);
-            return PFDR_OK;
-        }
-        std::unique_ptr<SimplexSession<real>> s(new SimplexSession<real>(&p));
-        if (verbose) { printf("done.\nPreconditioned forward-Douglas-Rachford algorithm\n"); fflush(stdout); }
-        tr.setup_done();
-        s->run(itMax);
-        tr.run_done();
-        int its = 0;
-        s->result(P, &its, Obj, Dif);
-        if (it) *it = its;
-        s.reset();
-        tr.finish(V, E, 0, K, its);
-    } catch (const HipError &h) {
-        return report_error(fn, h);
-    } catch (const std::exception &ex) {
-        return report_error(fn, ex.what());
-    }
-    return PFDR_OK;
+    return solve_one_call<SimplexSession<real>>(fn, p, P, it, Obj, Dif, 0, K, true);
 }
 
 template <typename real>
