@@ -810,6 +810,71 @@ void check_permutation(const int *lab, int V, long Vglob, Transport &tr, hipStre
     if (nb) throw std::runtime_error("vtx_label of the ranks is not a permutation of [0, V_global)");
 }
 
+// the caller's labels of this rank's V owned vertices (pfdr_problem.vtx_label,
+// in host or device memory by mem) as checked 32-bit labels, returned and
+// copied to dev; collective (check_permutation)
+std::vector<int> caller_labels(const int64_t *vtx_label, int mem, int V, long Vglob,
+                               DevBuf<int> &dev, Transport &tr, hipStream_t s) {
+    std::vector<int64_t> h64(V);
+    PFDR_HIP(hipMemcpy(h64.data(), vtx_label, sizeof(int64_t) * V,
+                       mem == PFDR_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    std::vector<int> h32(V);
+    for (int v = 0; v < V; v++) {
+        if (h64[v] < 0 || h64[v] >= Vglob) throw std::runtime_error("vtx_label outside [0, V_global)");
+        h32[v] = (int)h64[v];
+    }
+    dev.alloc(V);
+    PFDR_HIP(hipMemcpy(dev.p, h32.data(), sizeof(int) * V, hipMemcpyHostToDevice));
+    check_permutation(dev.p, V, Vglob, tr, s);
+    return h32;
+}
+
+// TermRoute's two kernels (pfdr_halo.hpp): compiled here alone, so that a
+// quadratic and a simplex session launch the same code object
+template <typename real>
+__global__ void k_route_pack(long n, int W, int nsum, const int *__restrict__ sidx,
+                             const real *__restrict__ terms, long tstride,
+                             real *__restrict__ buf) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * W) return;
+    const long j = t / W;
+    const int w = (int)(t - j * W);
+    const long v = sidx[j];
+    for (int y = 0; y < nsum; y++) buf[(j * nsum + y) * W + w] = terms[y * tstride + v * W + w];
+}
+template <typename real>
+__global__ void k_route_unpack(long n, int W, int nsum, const int *__restrict__ rpos,
+                               const real *__restrict__ buf, real *__restrict__ slice,
+                               long sstride) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * W) return;
+    const long j = t / W;
+    const int w = (int)(t - j * W);
+    const long p = rpos[j];
+    for (int y = 0; y < nsum; y++) slice[y * sstride + p * W + w] = buf[(j * nsum + y) * W + w];
+}
+
+template <typename real>
+void route_pack(long n, int W, int nsum, const int *sidx, const real *terms, long tstride,
+                real *buf, hipStream_t s) {
+    k_route_pack<real><<<grid_for(n * W), kBlock, 0, s>>>(n, W, nsum, sidx, terms, tstride, buf);
+    PFDR_HIP(hipGetLastError());
+}
+template <typename real>
+void route_unpack(long n, int W, int nsum, const int *rpos, const real *buf, real *slice,
+                  long sstride, hipStream_t s) {
+    k_route_unpack<real><<<grid_for(n * W), kBlock, 0, s>>>(n, W, nsum, rpos, buf, slice, sstride);
+    PFDR_HIP(hipGetLastError());
+}
+template void route_pack<float>(long, int, int, const int *, const float *, long, float *,
+                                hipStream_t);
+template void route_pack<double>(long, int, int, const int *, const double *, long, double *,
+                                 hipStream_t);
+template void route_unpack<float>(long, int, int, const int *, const float *, float *, long,
+                                  hipStream_t);
+template void route_unpack<double>(long, int, int, const int *, const double *, double *, long,
+                                   hipStream_t);
+
 }  // namespace pfdr
 
 extern "C" int pfdr_loopback_create(void **hub_out, int nranks) {

@@ -179,6 +179,11 @@ void partition_setup(const pfdr_problem *p, int V, long E, std::unique_ptr<Halo>
 // vertices (vtx_label, device, V per rank) form a permutation of
 // [0, V_global); throws otherwise.
 void check_permutation(const int *lab, int V, long Vglob, Transport &tr, hipStream_t s);
+// The caller's labels of this rank's V owned vertices (pfdr_problem.vtx_label,
+// host or device memory by mem) parsed into 32-bit labels in [0, Vglob):
+// returned, copied to dev (allocated here), and checked as above (collective).
+std::vector<int> caller_labels(const int64_t *vtx_label, int mem, int V, long Vglob,
+                               DevBuf<int> &dev, Transport &tr, hipStream_t s);
 
 // Contribution CSR of both solvers: the 2E local slots (address e = u end,
 // E + e = v end) keyed by (local vertex, 2 e_global + side) — the
@@ -244,28 +249,13 @@ struct ChainSum {
 
 // item j of the route: its W terms of every sum into the send buffer (items
 // grouped by destination), and back out of the receive buffer at its slot
+// (launches of pfdr_halo.hip's two kernels, which that unit alone compiles)
 template <typename real>
-__global__ void k_route_pack(long n, int W, int nsum, const int *__restrict__ sidx,
-                             const real *__restrict__ terms, long tstride,
-                             real *__restrict__ buf) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * W) return;
-    const long j = t / W;
-    const int w = (int)(t - j * W);
-    const long v = sidx[j];
-    for (int y = 0; y < nsum; y++) buf[(j * nsum + y) * W + w] = terms[y * tstride + v * W + w];
-}
+void route_pack(long n, int W, int nsum, const int *sidx, const real *terms, long tstride,
+                real *buf, hipStream_t s);
 template <typename real>
-__global__ void k_route_unpack(long n, int W, int nsum, const int *__restrict__ rpos,
-                               const real *__restrict__ buf, real *__restrict__ slice,
-                               long sstride) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * W) return;
-    const long j = t / W;
-    const int w = (int)(t - j * W);
-    const long p = rpos[j];
-    for (int y = 0; y < nsum; y++) slice[y * sstride + p * W + w] = buf[(j * nsum + y) * W + w];
-}
+void route_unpack(long n, int W, int nsum, const int *rpos, const real *buf, real *slice,
+                  long sstride, hipStream_t s);
 
 // Iterate-evolution sums of a RELABELLED partition (the ranks own ranges of
 // internal labels, while the reference sums in the caller's order).  The
@@ -333,11 +323,7 @@ struct TermRoute {
     void run(Transport &tr, const real *terms, long tstride, real *out, const int *halt,
              hipStream_t s) {
         const int n = nranks;
-        if (nsend) {
-            k_route_pack<real><<<grid_for(nsend * W), kBlock, 0, s>>>(nsend, W, nsum, sidx.p, terms,
-                                                                    tstride, sbuf.p);
-            PFDR_HIP(hipGetLastError());
-        }
+        if (nsend) route_pack<real>(nsend, W, nsum, sidx.p, terms, tstride, sbuf.p, s);
         const size_t ib = sizeof(real) * nsum * W;  // bytes per item
         std::vector<const void *> sp(n);
         std::vector<void *> rp(n);
@@ -351,11 +337,7 @@ struct TermRoute {
         tr.exchange(sp, sb, rp, rb, s);  // (skips this rank's own part)
         if (rb[rank])
             PFDR_HIP(hipMemcpyAsync(rp[rank], sp[rank], rb[rank], hipMemcpyDeviceToDevice, s));
-        if (nrecv) {
-            k_route_unpack<real><<<grid_for(nrecv * W), kBlock, 0, s>>>(nrecv, W, nsum, rpos.p,
-                                                                      rbuf.p, slice.p, sstride);
-            PFDR_HIP(hipGetLastError());
-        }
+        if (nrecv) route_unpack<real>(nrecv, W, nsum, rpos.p, rbuf.p, slice.p, sstride, s);
         chain.run(tr, slice.p, sstride, out, halt, s);
     }
 };

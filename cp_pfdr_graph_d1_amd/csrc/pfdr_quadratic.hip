@@ -423,18 +423,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
     Vglob_ = halo_ ? (long)halo_->off.back() : V_;
     if (p->vtx_label) {
         if (!halo_) throw std::runtime_error("vtx_label is for partitioned sessions");
-        std::vector<int64_t> h64(V_);
-        PFDR_HIP(hipMemcpy(h64.data(), p->vtx_label, sizeof(int64_t) * V_,
-                           p->mem == PFDR_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-        std::vector<int> h32(V_);
-        for (int v = 0; v < V_; v++) {
-            if (h64[v] < 0 || h64[v] >= Vglob_)
-                throw std::runtime_error("vtx_label outside [0, V_global)");
-            h32[v] = (int)h64[v];
-        }
-        lab_.alloc(V_);
-        PFDR_HIP(hipMemcpy(lab_.p, h32.data(), sizeof(int) * V_, hipMemcpyHostToDevice));
-        check_permutation(lab_.p, V_, Vglob_, *halo_->tr, s);
+        caller_labels(p->vtx_label, p->mem, V_, Vglob_, lab_, *halo_->tr, s);
     }
     if (mode_ == A_ATA && -(long)N_ != Vglob_)
         throw std::runtime_error("N < 0 requires A = A^tA (columns of the owned vertices, "

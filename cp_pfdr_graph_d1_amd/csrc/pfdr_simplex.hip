@@ -2579,18 +2579,9 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
         if (!halo_) dws_.alloc(mono_ws_bytes<real>(n, 1));
         red_.alloc(2);
         if (routed) {
-            std::vector<int64_t> h64(V_);
-            PFDR_HIP(hipMemcpy(h64.data(), p->vtx_label, sizeof(int64_t) * V_,
-                               mem == PFDR_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-            std::vector<int> h32(V_);
-            for (int v = 0; v < V_; v++) {
-                if (h64[v] < 0 || h64[v] >= Vglob_)
-                    throw std::runtime_error("vtx_label outside [0, V_global)");
-                h32[v] = (int)h64[v];
-            }
-            DevBuf<int> dl(V_);
-            PFDR_HIP(hipMemcpy(dl.p, h32.data(), sizeof(int) * V_, hipMemcpyHostToDevice));
-            check_permutation(dl.p, V_, Vglob_, *halo_->tr, s);
+            DevBuf<int> dl;
+            const std::vector<int> h32 =
+                caller_labels(p->vtx_label, mem, V_, Vglob_, dl, *halo_->tr, s);
             route_.init(h32, Vglob_, 1, track_ == 1 ? K_ : 1, *halo_->tr, s);
         } else if (halo_) {
             chain_.init(nterms_, 1, *halo_->tr);
