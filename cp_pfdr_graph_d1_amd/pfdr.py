@@ -239,6 +239,17 @@ def _is_device(a):
     return hasattr(a, "data_ptr")
 
 
+def _cp_stats(fill, first="n_cuts"):
+    """the cut pursuits' seconds[6] / counts[4] record, which ``fill(seconds,
+    counts)`` writes -> dict: seconds per phase and counts"""
+    sec = np.zeros(6, np.float64)
+    cnt = np.zeros(4, np.int64)
+    fill(_ptr(sec, C.c_double), _ptr(cnt, C.c_int64))
+    out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
+    out.update(zip((first, "rounds", "relabels", "pfdr_it"), cnt.tolist()))
+    return out
+
+
 class CSC:
     """A sparse N-by-V observation operator in compressed sparse columns
     (``pfdr_csc``, include/pfdr_mi355x.h): column v holds the entries
@@ -377,64 +388,24 @@ class Lib:
                   C.c_int(verbose)), "pfdr_quadratic_d1_l1_" + sfx)
         return X, it.value, Obj, Dif
 
-    def cp_quadratic_d1_l1(self, V, N, Y, A, Eu, Ev, La_d1, La_l1=None, positivity=0,
-                           CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
-                           difTol=1e-4, itMax=10000, verbose=0, _entry="pfdr_cp_quadratic_d1_l1_"):
-        """pfdr_cp_quadratic_d1_l1: the whole cut pursuit -> (Cv[V] int32,
-        rX[rV], CP_it, Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1])"""
-        Y = np.ascontiguousarray(Y)
-        ct, sfx, _ = _real(Y.dtype)
-        dt = Y.dtype
-        A, La_d1, La_l1 = (_arr(a, dt) for a in (A, La_d1, La_l1))
-        Eu, Ev = _arr(Eu, np.int32), _arr(Ev, np.int32)
-        V = int(V)
-        Cv = np.zeros(V, np.int32)
-        rX = np.zeros(V, dt)
-        Obj = np.zeros(CP_itMax + 1, dt)
-        Dif = np.zeros(max(CP_itMax, 1), dt)
-        Time = np.zeros(CP_itMax + 1, np.float64)
-        rV, it = C.c_int(0), C.c_int(0)
-        fn = getattr(self.lib, _entry + sfx)
-        _check(fn(C.c_int(V), C.c_int(Eu.size), C.c_int(N), C.byref(rV), _ptr(Cv, C.c_int),
-                  _ptr(rX, ct), _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int), _ptr(Ev, C.c_int),
-                  _ptr(La_d1, ct), _ptr(La_l1, ct), C.c_int(int(positivity)), ct(CP_difTol),
-                  C.c_int(CP_itMax), C.byref(it), ct(rho), ct(condMin), ct(difRcd), ct(difTol),
-                  C.c_int(itMax), _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct),
-                  C.c_int(verbose)), _entry + sfx)
-        return Cv, rX[:rV.value].copy(), it.value, Obj, Dif[:CP_itMax], Time
-
-    def cp_quadratic_d1_l1_duplex(self, V, N, Y, A, Eu, Ev, La_d1, La_l1=None, positivity=0,
-                                  CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3,
-                                  difRcd=0.0, difTol=1e-4, itMax=10000, verbose=0):
-        """pfdr_cp_quadratic_d1_l1_duplex: the duplex driver's whole cut pursuit
-        (one two-layer cut per iteration); arguments and returns as
-        cp_quadratic_d1_l1"""
-        return self.cp_quadratic_d1_l1(V, N, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
-                                       CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose,
-                                       _entry="pfdr_cp_quadratic_d1_l1_duplex_")
-
-    def cp_quadratic_d1_l1_duplex_stats(self):
-        """pfdr_cp_quadratic_d1_l1_duplex_stats of this thread's last
-        cp_quadratic_d1_l1_duplex -> dict: seconds per phase and counts"""
-        sec = np.zeros(6, np.float64)
-        cnt = np.zeros(4, np.int64)
-        _check(self.lib.pfdr_cp_quadratic_d1_l1_duplex_stats(
-            _ptr(sec, C.c_double), _ptr(cnt, C.c_int64)), "pfdr_cp_quadratic_d1_l1_duplex_stats")
-        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
-        out.update(zip(("n_cuts", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
-        return out
-
-    def cp_quadratic_d1_bounds(self, V, N, Y, A, Eu, Ev, La_d1, lo=-np.inf, hi=np.inf,
-                               CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
-                               difTol=1e-4, itMax=10000, verbose=0):
-        """pfdr_cp_quadratic_d1_bounds: the bounds driver's whole cut pursuit for
-        the box lo <= x <= hi (+-inf: no bound) -> (Cv[V] int32, rX[rV], CP_it,
-        Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1])"""
+    def _cp_quadratic(self, flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho,
+                      condMin, difRcd, difTol, itMax, verbose):
+        """the quadratic cut-pursuit entries' one call; ``own``, the flavour's
+        own arguments: (La_l1, positivity) for "l1" and "duplex", (lo, hi) for
+        "bounds" -> (Cv[V] int32, rX[rV], CP_it, Obj[CP_itMax + 1],
+        Dif[CP_itMax], Time[CP_itMax + 1])"""
         Y = np.ascontiguousarray(Y)
         ct, sfx, _ = _real(Y.dtype)
         dt = Y.dtype
         A, La_d1 = (_arr(a, dt) for a in (A, La_d1))
         Eu, Ev = _arr(Eu, np.int32), _arr(Ev, np.int32)
+        if flavour == "bounds":
+            name = "pfdr_cp_quadratic_d1_bounds_" + sfx
+            own = (ct(own[0]), ct(own[1]))
+        else:
+            name = "pfdr_cp_quadratic_d1_l1_" + ("duplex_" if flavour == "duplex" else "") + sfx
+            La_l1 = _arr(own[0], dt)
+            own = (_ptr(La_l1, ct), C.c_int(int(own[1])))
         V, CP_itMax = int(V), int(CP_itMax)
         Cv = np.zeros(V, np.int32)
         rX = np.zeros(V, dt)
@@ -442,25 +413,55 @@ class Lib:
         Dif = np.zeros(max(CP_itMax, 1), dt)
         Time = np.zeros(CP_itMax + 1, np.float64)
         rV, it = C.c_int(0), C.c_int(0)
-        fn = getattr(self.lib, "pfdr_cp_quadratic_d1_bounds_" + sfx)
-        _check(fn(C.c_int(V), C.c_int(Eu.size), C.c_int(N), C.byref(rV), _ptr(Cv, C.c_int),
-                  _ptr(rX, ct), _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int), _ptr(Ev, C.c_int),
-                  _ptr(La_d1, ct), ct(lo), ct(hi), ct(CP_difTol), C.c_int(CP_itMax),
-                  C.byref(it), ct(rho), ct(condMin), ct(difRcd), ct(difTol), C.c_int(itMax),
-                  _ptr(Time, C.c_double), _ptr(Obj, ct), _ptr(Dif, ct), C.c_int(verbose)),
-               "pfdr_cp_quadratic_d1_bounds_" + sfx)
+        _check(getattr(self.lib, name)(
+            C.c_int(V), C.c_int(Eu.size), C.c_int(N), C.byref(rV), _ptr(Cv, C.c_int),
+            _ptr(rX, ct), _ptr(Y, ct), _ptr(A, ct), _ptr(Eu, C.c_int), _ptr(Ev, C.c_int),
+            _ptr(La_d1, ct), *own, ct(CP_difTol), C.c_int(CP_itMax), C.byref(it), ct(rho),
+            ct(condMin), ct(difRcd), ct(difTol), C.c_int(itMax), _ptr(Time, C.c_double),
+            _ptr(Obj, ct), _ptr(Dif, ct), C.c_int(verbose)), name)
         return Cv, rX[:rV.value].copy(), it.value, Obj, Dif[:CP_itMax], Time
+
+    def cp_quadratic_d1_l1(self, V, N, Y, A, Eu, Ev, La_d1, La_l1=None, positivity=0,
+                           CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
+                           difTol=1e-4, itMax=10000, verbose=0):
+        """pfdr_cp_quadratic_d1_l1: the whole cut pursuit -> (Cv[V] int32,
+        rX[rV], CP_it, Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1])"""
+        return self._cp_quadratic("l1", V, N, Y, A, Eu, Ev, La_d1, (La_l1, positivity),
+                                  CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax,
+                                  verbose)
+
+    def cp_quadratic_d1_l1_duplex(self, V, N, Y, A, Eu, Ev, La_d1, La_l1=None, positivity=0,
+                                  CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3,
+                                  difRcd=0.0, difTol=1e-4, itMax=10000, verbose=0):
+        """pfdr_cp_quadratic_d1_l1_duplex: the duplex driver's whole cut pursuit
+        (one two-layer cut per iteration); arguments and returns as
+        cp_quadratic_d1_l1"""
+        return self._cp_quadratic("duplex", V, N, Y, A, Eu, Ev, La_d1, (La_l1, positivity),
+                                  CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax,
+                                  verbose)
+
+    def cp_quadratic_d1_l1_duplex_stats(self):
+        """pfdr_cp_quadratic_d1_l1_duplex_stats of this thread's last
+        cp_quadratic_d1_l1_duplex -> dict: seconds per phase and counts"""
+        return _cp_stats(lambda sec, cnt: _check(
+            self.lib.pfdr_cp_quadratic_d1_l1_duplex_stats(sec, cnt),
+            "pfdr_cp_quadratic_d1_l1_duplex_stats"))
+
+    def cp_quadratic_d1_bounds(self, V, N, Y, A, Eu, Ev, La_d1, lo=-np.inf, hi=np.inf,
+                               CP_difTol=1e-3, CP_itMax=10, rho=1.0, condMin=1e-3, difRcd=0.0,
+                               difTol=1e-4, itMax=10000, verbose=0):
+        """pfdr_cp_quadratic_d1_bounds: the bounds driver's whole cut pursuit for
+        the box lo <= x <= hi (+-inf: no bound) -> (Cv[V] int32, rX[rV], CP_it,
+        Obj[CP_itMax + 1], Dif[CP_itMax], Time[CP_itMax + 1])"""
+        return self._cp_quadratic("bounds", V, N, Y, A, Eu, Ev, La_d1, (lo, hi), CP_difTol,
+                                  CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose)
 
     def cp_quadratic_d1_bounds_stats(self):
         """pfdr_cp_quadratic_d1_bounds_stats of this thread's last
         cp_quadratic_d1_bounds -> dict: seconds per phase and counts"""
-        sec = np.zeros(6, np.float64)
-        cnt = np.zeros(4, np.int64)
-        _check(self.lib.pfdr_cp_quadratic_d1_bounds_stats(
-            _ptr(sec, C.c_double), _ptr(cnt, C.c_int64)), "pfdr_cp_quadratic_d1_bounds_stats")
-        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
-        out.update(zip(("n_cuts", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
-        return out
+        return _cp_stats(lambda sec, cnt: _check(
+            self.lib.pfdr_cp_quadratic_d1_bounds_stats(sec, cnt),
+            "pfdr_cp_quadratic_d1_bounds_stats"))
 
     def cp_loss_d1_simplex(self, K, Q, Eu, Ev, La_d1, al=0.1, CP_difTol=1e-3, CP_itMax=10,
                            rho=1.0, condMin=0.1, difRcd=0.0, difTol=1e-4, itMax=1000,
@@ -534,14 +535,10 @@ class Lib:
     def cp_loss_d1_simplex_stats(self, n_exp=64):
         """pfdr_cp_loss_d1_simplex_stats of this thread's last cp_loss_d1_simplex
         -> dict: seconds per phase, counts, rounds / relabels per expansion"""
-        sec = np.zeros(6, np.float64)
-        cnt = np.zeros(4, np.int64)
         er, el = np.zeros(n_exp, np.int64), np.zeros(n_exp, np.int64)
-        _check(self.lib.pfdr_cp_loss_d1_simplex_stats(
-            _ptr(sec, C.c_double), _ptr(cnt, C.c_int64), _ptr(er, C.c_int64),
-            _ptr(el, C.c_int64), C.c_int(n_exp)), "pfdr_cp_loss_d1_simplex_stats")
-        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
-        out.update(zip(("expansions", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
+        out = _cp_stats(lambda sec, cnt: _check(self.lib.pfdr_cp_loss_d1_simplex_stats(
+            sec, cnt, _ptr(er, C.c_int64), _ptr(el, C.c_int64), C.c_int(n_exp)),
+            "pfdr_cp_loss_d1_simplex_stats"), first="expansions")
         out["exp_rounds"] = er[er >= 0]
         out["exp_relabels"] = el[el >= 0]
         return out
@@ -660,26 +657,36 @@ def PFDR_graph_quadratic_d1_l1_AtA(AtY, AtA, Eu, Ev, La_d1, La_l1, positivity,
         obj, dif, verbose)
 
 
+def _l22_scale(Y, La_l2):
+    """the l22 wrappers' convention (octave/mex/PFDR_graph_l22_d1_l1_mex.cpp:54-83
+    and its counterparts): Y <- La_l2*Y, N = 0, A = La_l2 (diagonal; a scalar:
+    none) -> (dtype, V, La_l2 or None, La_l2*Y)"""
+    dt = np.result_type(Y, np.float32)
+    La_l2 = _scal_or_vec(La_l2, Y.size, dt)
+    return dt, Y.size, La_l2, (La_l2 * Y).astype(dt) if La_l2 is not None else Y.astype(dt)
+
+
+def _l22_correct(Obj, it, Y, La_l2, dt):
+    """... and Obj += 1/2 ||y||^2_La_l2, the constant the scaled problem leaves out"""
+    if Obj is not None:
+        y = Y.astype(dt)
+        w = La_l2 if La_l2 is not None else np.ones(Y.size, dt)
+        Obj[: it + 1] += float(np.sum(w.astype(np.float64) * y * y)) / 2.0
+
+
 def PFDR_graph_l22_d1_l1(Y, La_l2, Eu, Ev, La_d1, La_l1, positivity, rho,
                          condMin, difRcd, difTol, itMax, verbose=0,
                          obj=False, dif=False):
     """octave/mex/PFDR_graph_l22_d1_l1_mex.cpp:54-83: Y <- La_l2*Y, N = 0,
     A = La_l2 (diagonal), Ltype DIAG, L = La_l2; Obj += 1/2 ||y||^2_La_l2."""
     Y = np.asarray(Y)
-    dt = np.result_type(Y, np.float32)
-    V = Y.size
-    La_l2 = _scal_or_vec(La_l2, V, dt)
-    Yw = (La_l2 * Y).astype(dt) if La_l2 is not None else Y.astype(dt)
+    dt, V, La_l2, Yw = _l22_scale(Y, La_l2)
     Eu, Ev = _edges(Eu, Ev)
     X, it, Obj, Dif = Lib().quadratic_d1_l1(
         np.zeros(V, dt), Yw, La_l2, 0, Eu, Ev, np.asarray(La_d1, dt),
         _scal_or_vec(La_l1, V, dt), positivity, DIAG, La_l2, rho, condMin,
         difRcd, difTol, itMax, obj, dif, verbose)
-    if Obj is not None:
-        y = Y.astype(dt)
-        w = La_l2 if La_l2 is not None else np.ones(V, dt)
-        y2 = float(np.sum(w.astype(np.float64) * y * y)) / 2.0
-        Obj[: it + 1] += y2
+    _l22_correct(Obj, it, Y, La_l2, dt)
     return X, it, Obj, Dif
 
 
@@ -707,19 +714,13 @@ def PFDR_graph_l22_d1_bounds(Y, La_l2, Eu, Ev, La_d1, Bnd, rho, condMin,
                              dif=False):
     """octave/mex/PFDR_graph_l22_d1_bounds_mex.cpp."""
     Y = np.asarray(Y)
-    dt = np.result_type(Y, np.float32)
-    V = Y.size
-    La_l2 = _scal_or_vec(La_l2, V, dt)
-    Yw = (La_l2 * Y).astype(dt) if La_l2 is not None else Y.astype(dt)
+    dt, V, La_l2, Yw = _l22_scale(Y, La_l2)
     Eu, Ev = _edges(Eu, Ev)
     X, it, Obj, Dif = Lib().quadratic_d1_bounds(
         np.zeros(V, dt), Yw, La_l2, 0, Eu, Ev, np.asarray(La_d1, dt), Bnd[0],
         Bnd[1], DIAG, La_l2, rho, condMin, difRcd, difTol, itMax, obj, dif,
         verbose)
-    if Obj is not None:
-        y = Y.astype(dt)
-        w = La_l2 if La_l2 is not None else np.ones(V, dt)
-        Obj[: it + 1] += float(np.sum(w.astype(np.float64) * y * y)) / 2.0
+    _l22_correct(Obj, it, Y, La_l2, dt)
     return X, it, Obj, Dif
 
 
@@ -762,13 +763,16 @@ def CP_PFDR_graph_loss_d1_simplex(Q, al, Eu, Ev, La_d1, CP_difTol, CP_itMax, PFD
     return Cv, rP.reshape((K, rP.size // K), order="F"), it, Time, Obj, Dif
 
 
-def _cp_bounds(V, N, Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, rho, condMin, difRcd, difTol,
-               itMax, verbose, time, obj, dif):
-    """the three bounds front-ends' common call -> (Cv, rX, CP_it, Time, Obj, Dif),
-    the records not asked for None"""
+def _cp_front(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho, condMin, difRcd,
+              difTol, itMax, verbose, time, obj, dif):
+    """the bounds ("bounds", own = Bnd) and duplex ("duplex", own = (La_l1,
+    positivity)) front-ends' common call -> (Cv, rX, CP_it, Time, Obj, Dif), the
+    records not asked for None"""
     Eu, Ev = _edges(Eu, Ev)
-    Cv, rX, it, Obj, Dif, Time = Lib().cp_quadratic_d1_bounds(
-        V, N, Y, A, Eu, Ev, np.asarray(La_d1, Y.dtype), Bnd[0], Bnd[1], CP_difTol, CP_itMax, rho,
+    if flavour == "duplex":
+        own = (_scal_or_vec(own[0], V, Y.dtype), own[1])
+    Cv, rX, it, Obj, Dif, Time = Lib()._cp_quadratic(
+        flavour, V, N, Y, A, Eu, Ev, np.asarray(La_d1, Y.dtype), own, CP_difTol, CP_itMax, rho,
         condMin, difRcd, difTol, itMax, verbose)
     return Cv, rX, it, Time if time else None, Obj if obj else None, Dif if dif else None
 
@@ -785,9 +789,10 @@ def CP_PFDR_graph_quadratic_d1_bounds(Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_it
     A = np.asarray(A)
     dt = np.result_type(Y, np.float32)
     N, V = A.shape
-    return _cp_bounds(V, N, np.asarray(Y, dt).ravel(), np.asfortranarray(A, dt).ravel(order="F"),
-                      Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
-                      PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+    return _cp_front("bounds", V, N, np.asarray(Y, dt).ravel(),
+                     np.asfortranarray(A, dt).ravel(order="F"), Eu, Ev, La_d1, Bnd, CP_difTol,
+                     CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
+                     verbose, time, obj, dif)
 
 
 def CP_PFDR_graph_quadratic_d1_bounds_AtA(AtY, AtA, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax,
@@ -798,10 +803,10 @@ def CP_PFDR_graph_quadratic_d1_bounds_AtA(AtY, AtA, Eu, Ev, La_d1, Bnd, CP_difTo
     A^tA (V-by-V) and A^ty given, N = -V; Obj leaves the constant 1/2 ||y||^2 out."""
     dt = np.result_type(AtY, np.float32)
     V = np.asarray(AtY).size
-    return _cp_bounds(V, -V, np.asarray(AtY, dt).ravel(),
-                      np.asfortranarray(AtA, dt).ravel(order="F"), Eu, Ev, La_d1, Bnd, CP_difTol,
-                      CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
-                      verbose, time, obj, dif)
+    return _cp_front("bounds", V, -V, np.asarray(AtY, dt).ravel(),
+                     np.asfortranarray(AtA, dt).ravel(order="F"), Eu, Ev, La_d1, Bnd, CP_difTol,
+                     CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
+                     verbose, time, obj, dif)
 
 
 def CP_PFDR_graph_l22_d1_bounds(Y, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho,
@@ -810,30 +815,12 @@ def CP_PFDR_graph_l22_d1_bounds(Y, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMa
     """octave/mex/CP_PFDR_graph_l22_d1_bounds_mex.cpp:62-90: Y <- La_l2*Y, N = 0,
     A = La_l2 (diagonal; a scalar: none); Obj += 1/2 ||y||^2_La_l2."""
     Y = np.asarray(Y).ravel()
-    dt = np.result_type(Y, np.float32)
-    V = Y.size
-    La_l2 = _scal_or_vec(La_l2, V, dt)
-    Yw = (La_l2 * Y).astype(dt) if La_l2 is not None else Y.astype(dt)
-    Cv, rX, it, Time, Obj, Dif = _cp_bounds(
-        V, 0, Yw, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
-        PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
-    if Obj is not None:
-        y = Y.astype(dt)
-        w = La_l2 if La_l2 is not None else np.ones(V, dt)
-        Obj[: it + 1] += float(np.sum(w.astype(np.float64) * y * y)) / 2.0
+    dt, V, La_l2, Yw = _l22_scale(Y, La_l2)
+    Cv, rX, it, Time, Obj, Dif = _cp_front(
+        "bounds", V, 0, Yw, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho,
+        PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+    _l22_correct(Obj, it, Y, La_l2, dt)
     return Cv, rX, it, Time, Obj, Dif
-
-
-def _cp_duplex(V, N, Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, rho, condMin,
-               difRcd, difTol, itMax, verbose, time, obj, dif):
-    """the duplex front-ends' common call -> (Cv, rX, CP_it, Time, Obj, Dif),
-    the records not asked for None"""
-    Eu, Ev = _edges(Eu, Ev)
-    dt = Y.dtype
-    Cv, rX, it, Obj, Dif, Time = Lib().cp_quadratic_d1_l1_duplex(
-        V, N, Y, A, Eu, Ev, np.asarray(La_d1, dt), _scal_or_vec(La_l1, V, dt), positivity,
-        CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose)
-    return Cv, rX, it, Time if time else None, Obj if obj else None, Dif if dif else None
 
 
 def CP_PFDR_graph_quadratic_d1_l1_duplex(Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
@@ -850,9 +837,10 @@ def CP_PFDR_graph_quadratic_d1_l1_duplex(Y, A, Eu, Ev, La_d1, La_l1, positivity,
     A = np.asarray(A)
     dt = np.result_type(Y, np.float32)
     N, V = A.shape
-    return _cp_duplex(V, N, np.asarray(Y, dt).ravel(), np.asfortranarray(A, dt).ravel(order="F"),
-                      Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, PFDR_rho,
-                      PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+    return _cp_front("duplex", V, N, np.asarray(Y, dt).ravel(),
+                     np.asfortranarray(A, dt).ravel(order="F"), Eu, Ev, La_d1,
+                     (La_l1, positivity), CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
+                     PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
 
 
 def CP_PFDR_graph_l22_d1_l1_duplex(Y, La_l2, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
@@ -861,17 +849,11 @@ def CP_PFDR_graph_l22_d1_l1_duplex(Y, La_l2, Eu, Ev, La_d1, La_l1, positivity, C
     """octave/mex/CP_PFDR_graph_l22_d1_l1_duplex_mex.cpp:66-93: Y <- La_l2*Y,
     N = 0, A = La_l2 (diagonal; a scalar: none); Obj += 1/2 ||y||^2_La_l2."""
     Y = np.asarray(Y).ravel()
-    dt = np.result_type(Y, np.float32)
-    V = Y.size
-    La_l2 = _scal_or_vec(La_l2, V, dt)
-    Yw = (La_l2 * Y).astype(dt) if La_l2 is not None else Y.astype(dt)
-    Cv, rX, it, Time, Obj, Dif = _cp_duplex(
-        V, 0, Yw, La_l2, Eu, Ev, La_d1, La_l1, positivity, CP_difTol, CP_itMax, PFDR_rho,
-        PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
-    if Obj is not None:
-        y = Y.astype(dt)
-        w = La_l2 if La_l2 is not None else np.ones(V, dt)
-        Obj[: it + 1] += float(np.sum(w.astype(np.float64) * y * y)) / 2.0
+    dt, V, La_l2, Yw = _l22_scale(Y, La_l2)
+    Cv, rX, it, Time, Obj, Dif = _cp_front(
+        "duplex", V, 0, Yw, La_l2, Eu, Ev, La_d1, (La_l1, positivity), CP_difTol, CP_itMax,
+        PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+    _l22_correct(Obj, it, Y, La_l2, dt)
     return Cv, rX, it, Time, Obj, Dif
 
 
@@ -964,6 +946,23 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
     return X, it
 
 
+def _cp_binding(flavour, obs, source, target, edge_weight, A, l1_weight, positivity, *args):
+    """CP_quadratic_l1 and CP_quadratic_l1_duplex after their defaults; ``args``:
+    Lib._cp_quadratic's from CP_difTol on"""
+    dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
+                                                             A, l1_weight)
+    if mode == "sparse":
+        raise ValueError("cut pursuit takes a dense A: a CSC is for the PFDR entries")
+    if mode == "identity":
+        N, A = 0, None
+    elif mode == "diagonal":
+        N, obs, A = 0, (obs * A).astype(dt), (A * A).astype(dt)
+    else:
+        A = np.asfortranarray(A).ravel(order="F")
+    r = Lib()._cp_quadratic(flavour, V, N, obs, A, Eu, Ev, ew, (lw, positivity), *args)
+    return r[0].astype(np.uint32), r[1]
+
+
 def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0,
                     PFDR_rho=1.0, PFDR_condMin=1e-3, CP_difTol=1e-3, PFDR_difRcd=0.0,
                     PFDR_difTol=1e-4, CP_itMax=10, PFDR_itMax=10000, verbose=0):
@@ -973,23 +972,9 @@ def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0
     conventions (those of PFDR_quadratic_l1), the whole loop on the GPU
     (pfdr_cp_quadratic_d1_l1).  Returns (Cv, rX): the component of every
     vertex (uint32, as the binding) and the value of every component."""
-    dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
-                                                             A, l1_weight)
-    if mode == "sparse":
-        raise ValueError("cut pursuit takes a dense A: a CSC is for the PFDR entries")
-    lib = Lib()
-    kw = dict(positivity=positivity, CP_difTol=CP_difTol, CP_itMax=CP_itMax, rho=PFDR_rho,
-              condMin=PFDR_condMin, difRcd=PFDR_difRcd, difTol=PFDR_difTol, itMax=PFDR_itMax,
-              verbose=verbose)
-    if mode == "identity":
-        r = lib.cp_quadratic_d1_l1(V, 0, obs, None, Eu, Ev, ew, lw, **kw)
-    elif mode == "diagonal":
-        r = lib.cp_quadratic_d1_l1(V, 0, (obs * A).astype(dt), (A * A).astype(dt), Eu, Ev, ew,
-                                   lw, **kw)
-    else:
-        r = lib.cp_quadratic_d1_l1(V, N, obs, np.asfortranarray(A).ravel(order="F"), Eu, Ev, ew,
-                                   lw, **kw)
-    return r[0].astype(np.uint32), r[1]
+    return _cp_binding("l1", obs, source, target, edge_weight, A, l1_weight, positivity,
+                       CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
+                       PFDR_itMax, verbose)
 
 
 def CP_quadratic_l1_duplex(obs, source, target, edge_weight, A, l1_weight, positivity=0,
@@ -998,23 +983,9 @@ def CP_quadratic_l1_duplex(obs, source, target, edge_weight, A, l1_weight, posit
     """CP_quadratic_l1 through the duplex driver (one two-layer cut per
     iteration, pfdr_cp_quadratic_d1_l1_duplex): same signature, defaults, input
     conventions and returns."""
-    dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
-                                                             A, l1_weight)
-    if mode == "sparse":
-        raise ValueError("cut pursuit takes a dense A: a CSC is for the PFDR entries")
-    lib = Lib()
-    kw = dict(positivity=positivity, CP_difTol=CP_difTol, CP_itMax=CP_itMax, rho=PFDR_rho,
-              condMin=PFDR_condMin, difRcd=PFDR_difRcd, difTol=PFDR_difTol, itMax=PFDR_itMax,
-              verbose=verbose)
-    if mode == "identity":
-        r = lib.cp_quadratic_d1_l1_duplex(V, 0, obs, None, Eu, Ev, ew, lw, **kw)
-    elif mode == "diagonal":
-        r = lib.cp_quadratic_d1_l1_duplex(V, 0, (obs * A).astype(dt), (A * A).astype(dt), Eu, Ev,
-                                          ew, lw, **kw)
-    else:
-        r = lib.cp_quadratic_d1_l1_duplex(V, N, obs, np.asfortranarray(A).ravel(order="F"), Eu,
-                                          Ev, ew, lw, **kw)
-    return r[0].astype(np.uint32), r[1]
+    return _cp_binding("duplex", obs, source, target, edge_weight, A, l1_weight, positivity,
+                       CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
+                       PFDR_itMax, verbose)
 
 
 def proj_simplex_metric(X, M, A):
@@ -1772,12 +1743,9 @@ class CPSolver:
     def stats(self):
         """-> dict: seconds per phase and counts of the last run, and the seconds
         the constructor's setup took"""
-        sec = np.zeros(6, np.float64)
-        cnt = np.zeros(4, np.int64)
         setup = C.c_double(0)
-        self._L.cp_solver_stats(self._h, sec.ctypes.data, cnt.ctypes.data, C.addressof(setup))
-        out = dict(zip(("gradient", "cuts", "graph", "pfdr", "sums", "total"), sec.tolist()))
-        out.update(zip(("n_cuts", "rounds", "relabels", "pfdr_it"), cnt.tolist()))
+        out = _cp_stats(lambda sec, cnt: self._L.cp_solver_stats(self._h, sec, cnt,
+                                                                 C.addressof(setup)))
         out["setup"] = setup.value
         return out
 

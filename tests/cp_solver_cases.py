@@ -2,26 +2,22 @@
 four drivers, the resumable solver and the matching one-call entry over one
 dict, and the twins restarted from a solver's state."""
 import numpy as np
+import pytest
 
-import cp_bounds_twin as BT
-import cp_duplex_twin as DT
+pytest.register_assert_rewrite("cp_entry")  # its asserts report their values
+
+import cp_entry as E
 import cp_problems as P
 import cp_simplex_twin as ST
 import cp_twin as T
+from cp_fixtures import BNAMES, DNAMES, NAMES, SNAMES, iteration_state, load_case
 from cp_pfdr_graph_d1_amd import pfdr
-from test_cp_graph_oracle import BNAMES, DNAMES, NAMES, SNAMES, iteration_state, load_case
 
 F32, F64 = np.float32, np.float64
-# the iteration fixtures' recorder parameters (oracle.CPStepRef*.step defaults)
-STEP = dict(rho=1.5, condMin=1e-3, difRcd=0.0, difTol=1e-4, itMax=1000)
+same_bytes, STEP = E.same_bytes, E.STEP
 STEP_SIMPLEX = dict(rho=1.5, condMin=1e-3, difRcd=0.0, difTol=1e-3, itMax=1000)
 FIXTURES = [("l1", n) for n in NAMES] + [("bounds", n) for n in BNAMES] + \
            [("simplex", n) for n in SNAMES] + [("duplex", n) for n in DNAMES]
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def fixture_problem(kind, name):
@@ -86,23 +82,17 @@ def entry(p, **over):
     """the matching one-call entry -> (Cv, rX, CP_it, Obj, Dif, Time)"""
     q = dict(p)
     q.update(over)
-    L = pfdr.Lib()
-    kw = dict(CP_difTol=q["CP_difTol"], CP_itMax=q["CP_itMax"], rho=q["rho"],
-              condMin=q["condMin"], difRcd=q["difRcd"], difTol=q["PFDR_difTol"],
-              itMax=q["PFDR_itMax"])
-    if q["kind"] == "simplex":
-        return L.cp_loss_d1_simplex(q["K"], q["Y"], q["Eu"], q["Ev"], q["La_d1"], al=q["al"], **kw)
-    a = (q["V"], q["N"], q["Y"], q["A"], q["Eu"], q["Ev"], q["La_d1"])
-    if q["kind"] == "bounds":
-        return L.cp_quadratic_d1_bounds(*a, lo=q["lo"], hi=q["hi"], **kw)
-    fn = L.cp_quadratic_d1_l1_duplex if q["kind"] == "duplex" else L.cp_quadratic_d1_l1
-    return fn(*a, q["La_l1"], positivity=q["positivity"], **kw)
+    if q["kind"] != "simplex":
+        return E.entry(q["kind"], q)
+    return pfdr.Lib().cp_loss_d1_simplex(
+        q["K"], q["Y"], q["Eu"], q["Ev"], q["La_d1"], al=q["al"], CP_difTol=q["CP_difTol"],
+        CP_itMax=q["CP_itMax"], rho=q["rho"], condMin=q["condMin"], difRcd=q["difRcd"],
+        difTol=q["PFDR_difTol"], itMax=q["PFDR_itMax"])
 
 
 def twin(p, **over):
-    """the twin over the library's steps (cp_*twin.py) for a problem dict"""
-    mod = {"l1": T, "duplex": DT, "bounds": BT, "simplex": ST}[p["kind"]]
-    return mod.gpu_twin(p, **over)
+    """the twin over the library's steps (cp_twin.py, cp_simplex_twin.py) for a problem dict"""
+    return (ST if p["kind"] == "simplex" else T).gpu_twin(p, **over)
 
 
 def twin_restart(t, p, state):

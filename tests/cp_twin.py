@@ -1,4 +1,6 @@
-"""TEST INFRASTRUCTURE -- a step-composed twin of the one-call cut pursuit.
+"""TEST INFRASTRUCTURE -- a step-composed twin of the one-call quadratic cut
+pursuits, with the ``flavour`` of the driver it mirrors (QuadDriver,
+csrc/pfdr_cutpursuit.hip): "l1", "duplex" or "bounds".
 
 The loop of the reference's CP_PFDR_graph_quadratic_d1_l1
 (src/CP_PFDR_graph_quadratic_d1_l1.cpp), restated in plain
@@ -8,17 +10,42 @@ Python from the reference source over a small backend interface:
   (``pfdr.CPGraph``, ``pfdr.cp_reduce`` with its defaults, PFDR from zero
   through ``Lib.quadratic_d1_l1(..., Ltype=DIAG, L=...)``);
 * ``OracleBackend`` -- the C restatement (``oracle.Oracle("port")``) around a
-  maxflow the caller passes in; N = 0 only (the restatement has no operator
-  norm, and for N = 0 the metric L is rAA itself, :775-776).
+  maxflow the caller passes in, ``maxflow(tr_cap, r_cap) -> segments`` and, for
+  a two-layer cut, ``maxflow(tr_cap[2V], r_link[V], r_cap[E]) -> segments[2V]``;
+  N = 0 only (the restatement has no operator norm, and for N = 0 the metric L
+  is rAA itself, :775-776).
 
-What the twin itself restates (reference line numbers):
+The flavour is used where QuadDriver uses it, and nowhere else:
+
+* "duplex": CP_PFDR_graph_quadratic_d1_l1_duplex
+  (src/CP_PFDR_graph_quadratic_d1_l1_duplex.cpp), which differs from the l1
+  driver's source in the graph and the cut only.  With an l1 term or positivity
+  the cut block is one two-layer cut (:469-545), gradient -> capacities_duplex
+  -> two-layer maxflow -> activate_duplex; the differentiable case is the l1
+  driver's single cut, as in the entry.
+* "bounds": CP_PFDR_graph_quadratic_d1_bounds
+  (src/CP_PFDR_graph_quadratic_d1_bounds.cpp:206-973).  initialize() (:66-170)
+  projects the one-component least-squares value rY / rAA onto [min, max]
+  (:136-139), and the residual of the direct case is taken at the projected
+  value; one cut when min == -inf and max == inf (:392), otherwise two, +1_U
+  then -1_U, the second cut's capacities taken before the first cut's
+  activations (:427-529), from ``capacities_bounds``; PFDR is
+  PFDR_graph_quadratic_d1_bounds from zero with Ltype = DIAG (:824-836,
+  ``quadratic_d1_bounds``); for N = 0 L is rAA (:752-753).  The graph has no l1
+  term; eps (:246), CP_difTol^2 (:305), the iteration that activates nothing
+  (:535-542), preAt in integers (:648), the merge (:840-863), the residual
+  (:866-878) and the iterate evolution (:883-901) are the l1 loop's, whose
+  arithmetic the two sources share line for line.
+
+What the twin itself restates (l1 reference line numbers):
 
 * initialize() (:94-175): the one-component solution, every sum added one by
   one in ``real`` (the reference built without OpenMP), the residual
   R = Y - rA x0 of the direct case;
 * eps (:252) and CP_difTol^2 (:311), in ``real``;
-* one cut (differentiable) or two, the second cut's capacities taken before
-  the first cut's activations (:402-560);
+* the cut block as QuadDriver::loop spells it: the two-layer cut, one cut
+  (differentiable), or two, the second cut's capacities taken before the first
+  cut's activations (:402-560);
 * the iteration that activates nothing (:556-563);
 * preAt = N <= 0 or rV < (2 N PFDR_it) / (N + PFDR_it) in integers, PFDR_it
   from the previous PFDR call and PFDR_itMax before the first (:308, :671);
@@ -65,10 +92,13 @@ def matrix(N, V, A, dt):
 
 
 class OracleBackend:
-    """the C restatement's steps around ``maxflow(tr_cap, r_cap) -> segments``"""
+    """the C restatement's steps around ``maxflow``; lo, hi: the box of "bounds" """
 
-    def __init__(self, o, maxflow, V, Eu, Ev, La_d1, La_l1):
-        self.o, self.maxflow = o, maxflow
+    def __init__(self, o, maxflow, V, Eu, Ev, La_d1, La_l1=None, flavour="l1", lo=-np.inf,
+                 hi=np.inf):
+        self.o, self.maxflow, self.flavour = o, maxflow, flavour
+        real = np.asarray(La_d1).dtype.type  # the bounds as the driver holds them
+        self.lo, self.hi = real(lo), real(hi)
         self.V = int(V)
         self.Eu = np.ascontiguousarray(Eu, np.int32)
         self.Ev = np.ascontiguousarray(Ev, np.int32)
@@ -94,14 +124,29 @@ class OracleBackend:
                                       self.La_l1, self.act, self.Cv, self.Vc, self.rVc, self.rX)
 
     def capacities(self, cut, positivity):
+        if self.flavour == "bounds":
+            return self.o.cp_capacities_bounds(cut, self.La_d1, float(self.lo), float(self.hi),
+                                               self.act, self.Cv, self.rX, self.DfS)
         return self.o.cp_capacities(cut, self.La_d1, self.La_l1, positivity, self.act, self.Cv,
                                     self.rX, self.DfS)
+
+    def capacities_duplex(self, positivity):
+        """-> (tr[2V], link[V], rc[E])"""
+        return self.o.cp_capacities_duplex(self.La_d1, self.La_l1, positivity, self.act, self.Cv,
+                                           self.rX, self.DfS)
 
     def mincut(self, tr, rc):
         return self.maxflow(tr, rc)
 
+    def mincut_duplex(self, tr, link, rc):
+        return self.maxflow(tr, link, rc)
+
     def activate(self, seg):
         self.act, n = self.o.cp_activate(self.Eu, self.Ev, seg, self.act)
+        return n
+
+    def activate_duplex(self, seg):
+        self.act, n = self.o.cp_activate_duplex(self.V, self.Eu, self.Ev, seg, self.act)
         return n
 
     def components(self):
@@ -121,9 +166,10 @@ class OracleBackend:
 
     def pfdr(self, n, Y, A, rEu, rEv, rLa, rL1, positivity, L, rho, condMin, difRcd, difTol,
              itMax):
-        X, it, _, _ = self.o.quadratic_d1_l1(
-            np.zeros(L.size, L.dtype), Y, A, n, rEu, rEv, rLa, rL1, positivity, 1, L, rho,
-            condMin, difRcd, difTol, itMax)
+        own = (float(self.lo), float(self.hi)) if self.flavour == "bounds" else (rL1, positivity)
+        fn = self.o.quadratic_d1_bounds if self.flavour == "bounds" else self.o.quadratic_d1_l1
+        X, it, _, _ = fn(np.zeros(L.size, L.dtype), Y, A, n, rEu, rEv, rLa, *own, 1, L, rho,
+                         condMin, difRcd, difTol, itMax)
         return X, it
 
     def merge(self, eps, difTol):
@@ -137,9 +183,11 @@ class OracleBackend:
 class GpuBackend:
     """the library's per-step Python API, host arrays in and out"""
 
-    def __init__(self, V, Eu, Ev, La_d1, La_l1):
+    def __init__(self, V, Eu, Ev, La_d1, La_l1=None, flavour="l1", lo=-np.inf, hi=np.inf):
         from cp_pfdr_graph_d1_amd import pfdr
-        self.mod = pfdr
+        self.mod, self.flavour = pfdr, flavour
+        real = np.asarray(La_d1).dtype.type  # the bounds as the driver holds them
+        self.lo, self.hi = real(lo), real(hi)
         self.lib = pfdr.Lib()
         self.g = pfdr.CPGraph(V, Eu, Ev, La_d1, La_l1)
 
@@ -157,13 +205,25 @@ class GpuBackend:
         self.g.gradient(N, A, None if N > 0 else Y, R)
 
     def capacities(self, cut, positivity):
+        if self.flavour == "bounds":
+            return self.g.capacities_bounds(cut, float(self.lo), float(self.hi))
         return self.g.capacities(cut, positivity)
+
+    def capacities_duplex(self, positivity):
+        """-> (tr[2V], link[V], rc[E])"""
+        return self.g.capacities_duplex(positivity)
 
     def mincut(self, tr, rc):
         return self.g.mincut(tr, rc)[0]
 
+    def mincut_duplex(self, tr, link, rc):
+        return self.g.mincut_duplex(tr, link, rc)[0]
+
     def activate(self, seg):
         return self.g.activate(seg)
+
+    def activate_duplex(self, seg):
+        return self.g.activate_duplex(seg)
 
     def components(self):
         self.Cv, self.Vc, self.rVc = self.g.components()
@@ -177,10 +237,11 @@ class GpuBackend:
 
     def pfdr(self, n, Y, A, rEu, rEv, rLa, rL1, positivity, L, rho, condMin, difRcd, difTol,
              itMax):
-        X, it, _, _ = self.lib.quadratic_d1_l1(
-            np.zeros(L.size, L.dtype), Y, A, n, rEu, rEv, rLa, rL1, positivity,
-            Ltype=self.mod.DIAG, L=L, rho=rho, condMin=condMin, difRcd=difRcd,
-            difTol=difTol, itMax=itMax)
+        own = (float(self.lo), float(self.hi)) if self.flavour == "bounds" else (rL1, positivity)
+        fn = self.lib.quadratic_d1_bounds if self.flavour == "bounds" else self.lib.quadratic_d1_l1
+        X, it, _, _ = fn(np.zeros(L.size, L.dtype), Y, A, n, rEu, rEv, rLa, *own,
+                         Ltype=self.mod.DIAG, L=L, rho=rho, condMin=condMin, difRcd=difRcd,
+                         difTol=difTol, itMax=itMax)
         return X, it
 
     def merge(self, eps, difTol):
@@ -191,7 +252,8 @@ class GpuBackend:
 
 
 class Twin:
-    """the loop over one backend; ``track``: CP_difTol > 0 or Dif != NULL (:314)"""
+    """the loop over one backend, whose flavour and box it takes; ``track``:
+    CP_difTol > 0 or Dif != NULL (:314)"""
 
     def __init__(self, backend, V, N, Y, A, positivity=0, CP_difTol=1e-3, rho=1.0,
                  condMin=1e-3, difRcd=0.0, difTol=1e-4, itMax=10000, La_l1=None, track=True):
@@ -203,6 +265,7 @@ class Twin:
         self.La_l1 = None if La_l1 is None else np.ascontiguousarray(La_l1, self.dt)
         self.positivity = int(positivity)
         real = self.dt.type
+        self.flavour, self.lo, self.hi = backend.flavour, real(backend.lo), real(backend.hi)
         self.CP_difTol = real(CP_difTol)
         self.eps = real_eps(self.dt, CP_difTol)                      # :252
         self.difTol2 = self.CP_difTol * self.CP_difTol               # :311
@@ -233,7 +296,10 @@ class Twin:
             else:
                 rAA = real(V)                                        # :129
         rL1 = seq_sum(self.La_l1) if self.La_l1 is not None else real(0)
-        if rY > rL1:                                                 # :138-140
+        if self.flavour == "bounds":                                 # bounds :136-139
+            x0 = real(rY / rAA)
+            x0 = self.lo if x0 < self.lo else self.hi if x0 > self.hi else x0
+        elif rY > rL1:                                               # :138-140
             x0 = (rY - rL1) / rAA
         elif not self.positivity and rY < -rL1:
             x0 = (rY + rL1) / rAA
@@ -262,7 +328,16 @@ class Twin:
         rec = {}
         b.gradient(N, self.A, self.Y, self.R if N > 0 else None)     # :339-400
         segs = []
-        if self.La_l1 is None and not self.positivity:               # :402-440
+        two = self.flavour == "duplex" and (self.La_l1 is not None or bool(self.positivity))
+        if self.flavour == "bounds":                                 # bounds :392
+            one = self.lo == -np.inf and self.hi == np.inf
+        else:
+            one = self.La_l1 is None and not self.positivity
+        if two:                                                      # duplex :469-545
+            tr, link, rc = b.capacities_duplex(self.positivity)
+            segs.append(b.mincut_duplex(tr, link, rc))
+            w = b.activate_duplex(segs[0])
+        elif one:                                                    # :402-440
             tr, rc = b.capacities(0, 0)
             segs.append(b.mincut(tr, rc))
             w = b.activate(segs[0])
@@ -338,10 +413,12 @@ class Twin:
 
 
 def gpu_twin(p, track=True, **over):
-    """the twin over the library's steps for a cp_problems.problem() dict"""
+    """the twin over the library's steps for a cp_problems.problem() dict, of
+    the dict's flavour (``kind``)"""
     q = dict(p)
     q.update(over)
-    b = GpuBackend(q["V"], q["Eu"], q["Ev"], q["La_d1"], q["La_l1"])
+    b = GpuBackend(q["V"], q["Eu"], q["Ev"], q["La_d1"], q["La_l1"], q["kind"],
+                   q.get("lo", -np.inf), q.get("hi", np.inf))
     t = Twin(b, q["V"], q["N"], q["Y"], q["A"], positivity=q["positivity"],
              CP_difTol=q["CP_difTol"], rho=q["rho"], condMin=q["condMin"], difRcd=q["difRcd"],
              difTol=q["PFDR_difTol"], itMax=q["PFDR_itMax"], La_l1=q["La_l1"], track=track)

@@ -1,5 +1,5 @@
 """The step-composed twin of the bounds cut-pursuit driver
-(tests/cp_bounds_twin.py) against the reference's recorded iterations
+(tests/cp_twin.py, flavour "bounds") against the reference's recorded iterations
 (tests/golden/cp_bounds_*.npz), on the CPU.
 
 * Always: over the oracle backend, every recorded iteration of the ten
@@ -26,10 +26,10 @@ import numpy as np
 import pytest
 
 import cp_bounds_run_cases as RC
-import cp_bounds_twin as BT
+import cp_twin as T
 import cp_problems as P
+from cp_fixtures import BNAMES, iteration_state, load_case
 from oracle import CPStepRef, CPStepRefBounds
-from test_cp_graph_oracle import BNAMES, iteration_state, load_case
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 REF = os.path.join(ROOT, "oracle", "_ref")
@@ -43,9 +43,9 @@ ENTRIES = ("pfdr_cp_quadratic_d1_bounds_f32", "pfdr_cp_quadratic_d1_bounds_f64",
 
 def twin_for(o, maxflow, c):
     V = c["Y"].size
-    b = BT.OracleBackend(o, maxflow, V, c["Eu"], c["Ev"], c["La_d1"], c["lo"], c["hi"])
-    return BT.Twin(b, V, 0, c["Y"], c["A"], lo=c["lo"], hi=c["hi"], CP_difTol=c["CP_difTol"],
-                   **STEP)
+    b = T.OracleBackend(o, maxflow, V, c["Eu"], c["Ev"], c["La_d1"], None, "bounds", c["lo"],
+                        c["hi"])
+    return T.Twin(b, V, 0, c["Y"], c["A"], CP_difTol=c["CP_difTol"], **STEP)
 
 
 def case_problem(c, CP_itMax):

@@ -1,5 +1,5 @@
 """The step-composed twin of the duplex cut-pursuit driver
-(tests/cp_duplex_twin.py) against the reference's recorded iterations
+(tests/cp_twin.py, flavour "duplex") against the reference's recorded iterations
 (tests/golden/cp_duplex_*.npz), on the CPU.
 
 * Always: over the oracle backend, every recorded iteration of the eight
@@ -26,10 +26,10 @@ import numpy as np
 import pytest
 
 import cp_duplex_run_cases as RC
-import cp_duplex_twin as DT
+import cp_twin as T
 import cp_problems as P
+from cp_fixtures import DNAMES, iteration_state, load_case
 from oracle import CPStepRefDuplex
-from test_cp_graph_oracle import DNAMES, iteration_state, load_case
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 REF = os.path.join(ROOT, "oracle", "_ref")
@@ -40,10 +40,9 @@ HAVE_REF = os.path.exists(P.driver("duplex", "ref", REF)) and CPStepRefDuplex.av
 
 def twin_for(o, maxflow, c):
     V = c["Y"].size
-    b = DT.OracleBackend(o, maxflow, V, c["Eu"], c["Ev"], c["La_d1"], c["La_l1"],
-                         c["positivity"])
-    return DT.Twin(b, V, 0, c["Y"], c["A"], positivity=c["positivity"],
-                   CP_difTol=c["CP_difTol"], La_l1=c["La_l1"], **STEP)
+    b = T.OracleBackend(o, maxflow, V, c["Eu"], c["Ev"], c["La_d1"], c["La_l1"], "duplex")
+    return T.Twin(b, V, 0, c["Y"], c["A"], positivity=c["positivity"],
+                  CP_difTol=c["CP_difTol"], La_l1=c["La_l1"], **STEP)
 
 
 def case_problem(c, CP_itMax):
@@ -151,8 +150,7 @@ def test_twin_reproduces_the_chain_end_to_end(oracle_port, tmp_path, name):
 
 
 def test_differentiable_case_is_the_l1_twin(oracle_port):
-    """no l1 term, no positivity: the duplex backend and twin are cp_twin's"""
-    import cp_twin as T
+    """no l1 term, no positivity: the duplex flavour is the l1 flavour"""
     c, d = load_case(DNAMES[0])
     V = c["Y"].size
     seen = []
@@ -162,10 +160,9 @@ def test_differentiable_case_is_the_l1_twin(oracle_port):
         return (tr < 0).astype(np.uint8)
 
     recs = []
-    for B, W in ((T.OracleBackend, T.Twin), (DT.OracleBackend, DT.Twin)):
-        extra = () if B is T.OracleBackend else (0,)
-        b = B(oracle_port, maxflow, V, c["Eu"], c["Ev"], c["La_d1"], None, *extra)
-        recs.append(W(b, V, 0, c["Y"], c["A"], CP_difTol=c["CP_difTol"], **STEP).run(2)[1])
+    for flavour in ("l1", "duplex"):
+        b = T.OracleBackend(oracle_port, maxflow, V, c["Eu"], c["Ev"], c["La_d1"], None, flavour)
+        recs.append(T.Twin(b, V, 0, c["Y"], c["A"], CP_difTol=c["CP_difTol"], **STEP).run(2)[1])
     assert seen and all(n == V for n in seen)
     for a, b in zip(*recs):
         assert np.array_equal(a["Cv"], b["Cv"]) and a["rX"].tobytes() == b["rX"].tobytes()

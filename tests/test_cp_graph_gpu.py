@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import cp_cases as CC
-from test_cp_graph_oracle import (BNAMES, DNAMES, NAMES, SNAMES, expansion_segments,
+from cp_fixtures import (BNAMES, DNAMES, NAMES, SNAMES, expansion_segments,
                                   iteration_state, load_case)
 
 pytestmark = pytest.mark.gpu

@@ -23,9 +23,9 @@ import pytest
 import cp_problems as P
 import cp_simplex_run_cases as SR
 import cp_simplex_twin as ST
+from cp_fixtures import SNAMES, load_case
 from cp_pfdr_graph_d1_amd import pfdr
 from cp_pfdr_graph_d1_amd.graphs import grid_graph, uniform
-from test_cp_graph_oracle import SNAMES, load_case
 
 pytestmark = pytest.mark.gpu
 

@@ -28,8 +28,8 @@ import pytest
 import cp_problems as P
 import cp_simplex_run_cases as SR
 import cp_simplex_twin as ST
+from cp_fixtures import SNAMES, expansion_segments, iteration_state, load_case
 from oracle import CPStepRefSimplex
-from test_cp_graph_oracle import SNAMES, expansion_segments, iteration_state, load_case
 
 REF = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref")
 # the recorder's PFDR parameters: oracle.CPStepRefSimplex.step's defaults

@@ -21,9 +21,9 @@ import cp_duplex_run_cases as DRC
 import cp_problems as P
 import cp_solver_cases as SC
 import cp_twin as T
+from cp_fixtures import TIES
 from cp_pfdr_graph_d1_amd import pfdr
 from cp_solver_cases import F32, F64, same_bytes
-from test_mincut_duplex_gpu import TIES
 
 pytestmark = pytest.mark.gpu
 

@@ -25,8 +25,8 @@ import pytest
 import cp_problems as P
 import cp_run_cases as RC
 import cp_twin as T
+from cp_fixtures import NAMES, iteration_state, load_case
 from oracle import CPStepRef
-from test_cp_graph_oracle import NAMES, iteration_state, load_case
 
 REF = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref")
 # the recorder's PFDR parameters: oracle.CPStepRef.step's defaults

@@ -9,7 +9,10 @@ import subprocess
 import numpy as np
 import pytest
 
+pytest.register_assert_rewrite("cp_entry")  # its asserts report their values
+
 import cp_problems as P
+from cp_entry import constant, functional
 from cp_pfdr_graph_d1_amd import pfdr
 
 pytestmark = pytest.mark.gpu
@@ -44,38 +47,6 @@ def run_gpu(p, CP_itMax=None):
         positivity=p["positivity"], CP_difTol=p["CP_difTol"],
         CP_itMax=p["CP_itMax"] if CP_itMax is None else CP_itMax, rho=p["rho"],
         condMin=p["condMin"], difRcd=p["difRcd"], difTol=p["PFDR_difTol"], itMax=p["PFDR_itMax"])
-
-
-def functional(p, x):
-    """F(x) = 1/2 ||y - A x||^2 + sum_E w |x_u - x_v| + sum_V la |x_v| in f64, in the
-    form the driver's Obj uses: for N <= 0 the premultiplied one, 1/2 <x, AtA x> -
-    <x, Aty> (F minus the constant 1/2 ||y||^2)"""
-    x = np.asarray(x, np.float64)
-    Y = np.asarray(p["Y"], np.float64)
-    V, N = p["V"], p["N"]
-    if N > 0:
-        A = np.asarray(p["A"], np.float64).reshape(V, N).T  # column major N-by-V
-        f = 0.5 * np.sum((Y - A @ x) ** 2)
-    elif N < 0:
-        AA = np.asarray(p["A"], np.float64).reshape(V, V)
-        f = 0.5 * x @ (AA @ x) - x @ Y
-    else:
-        a = np.ones(V) if p["A"] is None else np.asarray(p["A"], np.float64)
-        f = np.sum(x * (0.5 * a * x - Y))
-    f += np.sum(np.asarray(p["La_d1"], np.float64) * np.abs(x[p["Eu"]] - x[p["Ev"]]))
-    if p["La_l1"] is not None:
-        f += np.sum(np.asarray(p["La_l1"], np.float64) * np.abs(x))
-    return float(f)
-
-
-def constant(p):
-    """1/2 ||y||^2, the term the premultiplied form of N = 0 lacks (the MEX
-    wrappers add it): Y = A^t y and the diagonal a of A^tA give y^2 = Y^2 / a"""
-    if p["N"] != 0:
-        return 0.0
-    Y = np.asarray(p["Y"], np.float64)
-    a = np.ones(p["V"]) if p["A"] is None else np.asarray(p["A"], np.float64)
-    return float(0.5 * np.sum(Y * Y / a))
 
 
 def components_connected(p, Cv, rV):

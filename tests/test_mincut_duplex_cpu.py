@@ -12,9 +12,9 @@ import pytest
 
 import cp_cases as CC
 import mincut_duplex_cases as MD
+from cp_fixtures import DNAMES, iteration_state, load_case
 from cp_pfdr_graph_d1_amd import pfdr
 from mincut_model import FORWARD, mincut_model
-from test_cp_graph_oracle import DNAMES, iteration_state, load_case
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 NEW = ("pfdr_cpgraph_mincut_duplex", "pfdr_cp_quadratic_d1_l1_duplex_f32",

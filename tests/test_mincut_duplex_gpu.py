@@ -19,21 +19,12 @@ import pytest
 import cp_cases as CC
 import mincut_cases as MC
 import mincut_duplex_cases as MD
+from cp_fixtures import DNAMES, TIES, iteration_state, load_case
 from cp_pfdr_graph_d1_amd import pfdr
 from oracle import CPStepRefDuplex
-from test_cp_graph_oracle import DNAMES, iteration_state, load_case
 from test_mincut_gpu import LARGE, REL, graph, large
 
 pytestmark = pytest.mark.gpu
-
-# Recorded cuts exempt from byte-equality: (fixture, iteration).  An entry is a
-# genuine tie between minimum cuts: its value in f64 equals the recorded one
-# within 1e-12 relative.  At most 4 of the 48.  Measured on an MI355X: 47 of 48
-# byte-equal; in this one, 10 nodes change side at a cut value that is the
-# recorded one to the last bit of f64 (f32 capacities; the f64 twin fixture and
-# the f64 numpy model return the recorded set).
-TIES = (("cp_duplex_grid2d_l1_f32", 4),)
-assert len(TIES) <= 4
 
 
 # ------------------------------------------------------------ 1. golden --

@@ -19,11 +19,11 @@ import pytest
 
 import cp_cases as CC
 import mincut_cases as MC
+from cp_fixtures import (BNAMES, NAMES, SNAMES, expansion_segments, iteration_state,
+                                  load_case)
 from cp_pfdr_graph_d1_amd import pfdr
 from cp_pfdr_graph_d1_amd.graphs import grid_graph, knn_jitter_grid
 from oracle import CPStepRef, CPStepRefSimplex
-from test_cp_graph_oracle import (BNAMES, NAMES, SNAMES, expansion_segments, iteration_state,
-                                  load_case)
 
 pytestmark = pytest.mark.gpu
 
