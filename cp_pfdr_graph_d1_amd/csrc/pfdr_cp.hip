@@ -15,9 +15,13 @@
 // differs: the reference's starts are time-seeded (:182), ours are fixed.
 // Large reduced problems (rV^2 N > 2^34 multiply-adds) compute rAA on the
 // matrix cores instead (pfdr_gram.hip; tolerance, not bit-exact).
+// A sparse A (N > 0, pfdr_cp_reduce_csc_*) changes the column-sum step only:
+// rA comes from the stored entries (pfdr_cp_sparse.hip) with the bytes of
+// k_cp_colsum on the densified matrix, and the rest runs on it as it is.
 #include <cmath>
 #include <stdexcept>
 
+#include "pfdr_cp_sparse.hpp"
 #include "pfdr_graph.hpp"
 #include "pfdr_session.hpp"
 
@@ -167,14 +171,15 @@ __global__ void k_cp_lipschitz(int rV, const real *__restrict__ l, real c, real 
     L[rv] = x;
 }
 
+// sp: the sparse A of N > 0 (A is then unused), already on the device
 template <typename real>
 static int cp_reduce_host(const char *fn, int N, int V, const real *A, const real *Y, int rV,
                           const int *rVc, const int *Vc, int preAt, int mem, real normTol,
                           int normItMax, int normNbInit, real *rA, real *rAA, real *rY, real *L,
-                          real *Leq) {
+                          real *Leq, CpCsc<real> *sp = nullptr) {
     if (V <= 0 || rV <= 0 || rV > V || !Y || !rVc || !Vc)
         return report_error(fn, "invalid arguments");
-    if (N > 0 && (!A || !rA)) return report_error(fn, "N > 0 needs A and rA");
+    if (N > 0 && ((!A && !sp) || !rA)) return report_error(fn, "N > 0 needs A and rA");
     if (N < 0 && (!A || -N != V)) return report_error(fn, "N < 0 needs A = A^tA and N = -V");
     if (N <= 0) preAt = 1;  // ref :671
     if (preAt && (!rAA || !rY)) return report_error(fn, "rAA and rY are required for this case");
@@ -218,7 +223,8 @@ static int cp_reduce_host(const char *fn, int N, int V, const real *A, const rea
         const dim3 b1(kBlock), gV(grid_for(rV));
         const dim3 gVV(grid_for(rV), gy);
         if (N > 0) {
-            k_cp_colsum<real><<<dim3(grid_for(N), gy), b1, 0, s>>>(N, rV, dA, dptr, dVc, drA);
+            if (sp) sp->colsum(rV, dptr, dVc, drA, s);
+            else k_cp_colsum<real><<<dim3(grid_for(N), gy), b1, 0, s>>>(N, rV, dA, dptr, dVc, drA);
             if (preAt) {
                 const double work = (double)rV * rV * N / 2;
                 if (work <= 17179869184.0) {
@@ -283,7 +289,56 @@ static int cp_reduce_host(const char *fn, int N, int V, const real *A, const rea
     return PFDR_OK;
 }
 
+template <typename real>
+int cp_reduce_sparse(CpCsc<real> &A, const real *Y, int rV, const int *rVc, const int *Vc,
+                     int preAt, real *rA, real *rAA, real *rY, real *L) {
+    return cp_reduce_host<real>("pfdr_cp_reduce_csc", A.N, A.V, nullptr, Y, rV, rVc, Vc, preAt,
+                                PFDR_MEM_DEVICE, real(1e-3), 100, 10, rA, rAA, rY, L, nullptr,
+                                &A);
+}
+template int cp_reduce_sparse<float>(CpCsc<float> &, const float *, int, const int *, const int *,
+                                     int, float *, float *, float *, float *);
+template int cp_reduce_sparse<double>(CpCsc<double> &, const double *, int, const int *,
+                                      const int *, int, double *, double *, double *, double *);
+
+// the public entry: the caller's CSC is copied in and checked first
+template <typename real>
+static int cp_reduce_csc(const char *fn, int N, int V, const pfdr_csc *A, const real *Y, int rV,
+                         const int *rVc, const int *Vc, int preAt, int mem, real normTol,
+                         int normItMax, int normNbInit, real *rA, real *rAA, real *rY, real *L,
+                         real *Leq) {
+    if (N <= 0) return report_error(fn, "a sparse A needs N > 0");
+    if (V <= 0 || (mem != PFDR_MEM_HOST && mem != PFDR_MEM_DEVICE))
+        return report_error(fn, "invalid arguments");
+    if (const char *bad = cp_csc_args(A)) return report_error(fn, bad);
+    CpCsc<real> sp;
+    try {
+        sp.take(N, V, A, mem, lib_stream());
+    } catch (const HipError &h) {
+        return report_error(fn, h);
+    } catch (const std::exception &ex) {
+        return report_error(fn, ex.what());
+    }
+    return cp_reduce_host<real>(fn, N, V, nullptr, Y, rV, rVc, Vc, preAt, mem, normTol, normItMax,
+                                normNbInit, rA, rAA, rY, L, Leq, &sp);
+}
+
 }  // namespace pfdr
+
+extern "C" int pfdr_cp_reduce_csc_f32(int N, int V, const pfdr_csc *A, const float *Y, int rV,
+                                      const int *rVc, const int *Vc, int preAt, int mem,
+                                      float normTol, int normItMax, int normNbInit, float *rA,
+                                      float *rAA, float *rY, float *L, float *Leq) {
+    return pfdr::cp_reduce_csc<float>("pfdr_cp_reduce_csc_f32", N, V, A, Y, rV, rVc, Vc, preAt,
+                                      mem, normTol, normItMax, normNbInit, rA, rAA, rY, L, Leq);
+}
+extern "C" int pfdr_cp_reduce_csc_f64(int N, int V, const pfdr_csc *A, const double *Y, int rV,
+                                      const int *rVc, const int *Vc, int preAt, int mem,
+                                      double normTol, int normItMax, int normNbInit, double *rA,
+                                      double *rAA, double *rY, double *L, double *Leq) {
+    return pfdr::cp_reduce_csc<double>("pfdr_cp_reduce_csc_f64", N, V, A, Y, rV, rVc, Vc, preAt,
+                                       mem, normTol, normItMax, normNbInit, rA, rAA, rY, L, Leq);
+}
 
 extern "C" int pfdr_cp_reduce_f32(int N, int V, const float *A, const float *Y, int rV,
                                   const int *rVc, const int *Vc, int preAt, int mem,

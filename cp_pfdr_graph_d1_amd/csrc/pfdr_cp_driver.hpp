@@ -72,6 +72,10 @@ struct CpDriverBase {
     int rV = 1;
     bool has_l1 = false;
     double setup_sums = 0;  // seconds of setup()'s sums; loop() leaves it alone
+    // Set before setup() by pfdr_cp_solver_create_sparse (quadratic drivers,
+    // N > 0, p.A null): the observation operator in CSC, arrays per p.mem;
+    // setup() copies it, and nothing reads the pointer afterwards.
+    const pfdr_csc *sparse = nullptr;
 
     // p.mem = PFDR_MEM_DEVICE: the arrays are device memory, copied except A,
     // which is borrowed.  want_obj: evaluate the functional at the initial state.

@@ -15,6 +15,7 @@
 #include <stdexcept>
 
 #include "pfdr_cp_driver.hpp"
+#include "pfdr_cp_sparse.hpp"
 
 namespace pfdr {
 
@@ -259,10 +260,9 @@ using pfdr::report_error;
     }                                                       \
     return PFDR_OK;
 
-extern "C" int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem *p) {
-    const char *fn = "pfdr_cp_solver_create";
-    if (!out || !p) return report_error(fn, "invalid arguments");
-    *out = nullptr;
+// csc: the sparse A of pfdr_cp_solver_create_sparse, whose own checks are done
+static int cps_create(const char *fn, pfdr_cp_solver **out, const pfdr_cp_problem *p,
+                      const pfdr_csc *csc) {
     if ((p->dtype != PFDR_F32 && p->dtype != PFDR_F64) ||
         (p->mem != PFDR_MEM_HOST && p->mem != PFDR_MEM_DEVICE) ||
         (p->kind != PFDR_KIND_L1 && p->kind != PFDR_KIND_BOUNDS && p->kind != PFDR_KIND_SIMPLEX))
@@ -274,7 +274,7 @@ extern "C" int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem
             return report_error(fn, "invalid arguments");
         if (!(p->al >= 0.0 && p->al <= 1.0)) return report_error(fn, "al must lie in [0, 1]");
     } else {
-        if (p->N != 0 && !p->A) return report_error(fn, "N != 0 needs A");
+        if (p->N != 0 && !p->A && !csc) return report_error(fn, "N != 0 needs A");
         if (p->N < 0 && -p->N != p->V)
             return report_error(fn, "N < 0 needs A = A^tA and N = -V");
         if (p->kind == PFDR_KIND_BOUNDS) {
@@ -295,7 +295,9 @@ extern "C" int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem
         h->d.reset(p->kind == PFDR_KIND_L1       ? pfdr::cp_make_l1_driver(p->dtype, p->duplex != 0)
                    : p->kind == PFDR_KIND_BOUNDS ? pfdr::cp_make_bounds_driver(p->dtype)
                                                  : pfdr::cp_make_simplex_driver(p->dtype));
+        h->d->sparse = csc;
         h->d->setup(*p, true);
+        h->d->sparse = nullptr;
         h->setup_seconds =
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         *out = h.release();
@@ -307,6 +309,26 @@ extern "C" int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem
         return report_error(fn, ex.what());
     }
     return PFDR_OK;
+}
+
+extern "C" int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem *p) {
+    const char *fn = "pfdr_cp_solver_create";
+    if (!out || !p) return report_error(fn, "invalid arguments");
+    *out = nullptr;
+    return cps_create(fn, out, p, nullptr);
+}
+
+extern "C" int pfdr_cp_solver_create_sparse(pfdr_cp_solver **out, const pfdr_cp_problem *p,
+                                            const pfdr_csc *A) {
+    const char *fn = "pfdr_cp_solver_create_sparse";
+    if (!out || !p) return report_error(fn, "invalid arguments");
+    *out = nullptr;
+    if (p->kind == PFDR_KIND_SIMPLEX)
+        return report_error(fn, "a sparse A: the simplex kind has no A");
+    if (p->N <= 0) return report_error(fn, "a sparse A needs N > 0");
+    if (p->A) return report_error(fn, "a sparse A and p->A are both set");
+    if (const char *bad = pfdr::cp_csc_args(A)) return report_error(fn, bad);
+    return cps_create(fn, out, p, A);
 }
 
 extern "C" void pfdr_cp_solver_destroy(pfdr_cp_solver *h) {

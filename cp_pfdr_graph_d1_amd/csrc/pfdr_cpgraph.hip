@@ -44,6 +44,7 @@
 #include <rocprim/rocprim.hpp>
 #include <stdexcept>
 
+#include "pfdr_cp_sparse.hpp"
 #include "pfdr_graph.hpp"
 #include "pfdr_mincut.hpp"
 #include "pfdr_monosum.hpp"
@@ -1122,6 +1123,8 @@ struct CpGraphBase {
     virtual void reduced_graph(double eps) = 0;
     virtual int merge(double eps, double difTol) = 0;
     virtual void gradient(int N, const void *A, const void *Y, const void *R, int mem) = 0;
+    // N > 0 with a sparse A (a CpCsc of the graph's real type), R on the device
+    virtual void gradient_sparse(const void *A, const void *R) = 0;
     virtual void capacities(int cut, int positivity, void *tr, void *rc, int mem) = 0;
     // bounds driver: box [mn, mx] (+-HUGE_VAL for none) instead of l1 / positivity
     virtual void capacities_bounds(int cut, double mn, double mx, void *tr, void *rc,
@@ -1456,6 +1459,19 @@ struct CpGraph : CpGraphBase {
         }
         k_cp_grad<real><<<grid_for(V), kBlock, 0, s>>>(V, mode, dA, dY, inc.ptr.p, inc.idx.p, Eu.p,
                                                        Ev.p, active.p, La.p,
+                                                       has_l1 ? L1.p : nullptr, Cv.p, rX.p, DfS.p);
+        PFDR_HIP(hipGetLastError());
+        PFDR_HIP(hipStreamSynchronize(s));
+    }
+
+    void gradient_sparse(const void *A, const void *R) override {
+        if (!rX.p) throw std::runtime_error("gradient: set the component values first");
+        const auto &sp = *(const CpCsc<real> *)A;
+        if (sp.V != V || !R) throw std::runtime_error("gradient: a sparse A needs V columns and R");
+        DfS.alloc(V);
+        sp.gradient((const real *)R, DfS.p, s);
+        k_cp_grad<real><<<grid_for(V), kBlock, 0, s>>>(V, 2, nullptr, nullptr, inc.ptr.p, inc.idx.p,
+                                                       Eu.p, Ev.p, active.p, La.p,
                                                        has_l1 ? L1.p : nullptr, Cv.p, rX.p, DfS.p);
         PFDR_HIP(hipGetLastError());
         PFDR_HIP(hipStreamSynchronize(s));
@@ -1932,6 +1948,42 @@ extern "C" int pfdr_cpgraph_gradient(pfdr_cpgraph *h, int N, const void *A, cons
     if (!h) return report_error("pfdr_cpgraph_gradient", "null graph");
     CPG_TRY("pfdr_cpgraph_gradient", {
         h->g->gradient(N, A, Y, R, mem);
+        if (DfS) h->g->get_dfs(DfS, mem);
+    })
+}
+
+int pfdr::cpgraph_gradient_sparse(pfdr_cpgraph *h, const void *A, const void *R) {
+    if (!h || !A) return report_error("pfdr_cpgraph_gradient_csc", "invalid arguments");
+    CPG_TRY("pfdr_cpgraph_gradient_csc", h->g->gradient_sparse(A, R))
+}
+
+template <typename real>
+static void cpg_gradient_csc(pfdr::CpGraphBase *g, int N, const pfdr_csc *A, const void *R,
+                             int mem) {
+    using namespace pfdr;
+    CpCsc<real> sp;
+    sp.take(N, g->V, A, mem, g->s);
+    DevBuf<real> bR;
+    const void *dR = R;
+    if (mem != PFDR_MEM_DEVICE) {
+        bR.alloc(N);
+        PFDR_HIP(hipMemcpyAsync(bR.p, R, sizeof(real) * N, hipMemcpyHostToDevice, g->s));
+        dR = bR.p;
+    }
+    g->gradient_sparse(&sp, dR);
+}
+
+extern "C" int pfdr_cpgraph_gradient_csc(pfdr_cpgraph *h, int N, const pfdr_csc *A, const void *R,
+                                         int mem, void *DfS) {
+    const char *fn = "pfdr_cpgraph_gradient_csc";
+    if (!h) return report_error(fn, "null graph");
+    if (N <= 0) return report_error(fn, "a sparse A needs N > 0");
+    if (!R || (mem != PFDR_MEM_HOST && mem != PFDR_MEM_DEVICE))
+        return report_error(fn, "invalid arguments");
+    if (const char *bad = pfdr::cp_csc_args(A)) return report_error(fn, bad);
+    CPG_TRY(fn, {
+        if (h->g->dtype == PFDR_F32) cpg_gradient_csc<float>(h->g, N, A, R, mem);
+        else cpg_gradient_csc<double>(h->g, N, A, R, mem);
         if (DfS) h->g->get_dfs(DfS, mem);
     })
 }

@@ -39,6 +39,7 @@
 #include <limits>
 
 #include "pfdr_cp_driver.hpp"
+#include "pfdr_cp_sparse.hpp"
 
 namespace pfdr {
 
@@ -176,6 +177,7 @@ struct QuadDriver : CpDriverBase {
     // the resident problem
     DevBuf<real> dY, dA;
     const real *pA = nullptr;  // dA, or the caller's device A
+    CpCsc<real> sp;            // the copy of a sparse A (N > 0), when the problem came with one
     int positivity = 0;                // l1, duplex
     real min = real(0), max = real(0);  // bounds
     // the state besides the graph's: values, Cv, residual (N > 0)
@@ -212,7 +214,7 @@ struct QuadDriver : CpDriverBase {
             HostPins hp(s);
             const size_t asz = N > 0 ? (size_t)N * V : N < 0 ? (size_t)V * V : A ? (size_t)V : 0;
             cp_take(dY, Y, N > 0 ? (size_t)N : (size_t)V, p.mem, hp, s);
-            if (!dev) cp_take(dA, A, asz, p.mem, hp, s);
+            if (!dev && !sparse) cp_take(dA, A, asz, p.mem, hp, s);
             cp_take(dEu, p.Eu, (size_t)E, p.mem, hp, s);
             cp_take(dEv, p.Ev, (size_t)E, p.mem, hp, s);
             cp_take(dLa, (const real *)p.La_d1, (size_t)E, p.mem, hp, s);
@@ -220,6 +222,7 @@ struct QuadDriver : CpDriverBase {
             hp.release();
         }
         pA = !A ? nullptr : dev ? A : dA.p;
+        if (sparse) sp.take(N, V, sparse, p.mem, s);
         CP_ABI(pfdr_cpgraph_create(&g, dt, V, E, dEu.p, dEv.p, dLa.p, has_l1 ? dL1.p : nullptr,
                                    PFDR_MEM_DEVICE));
 
@@ -231,7 +234,8 @@ struct QuadDriver : CpDriverBase {
             drA0.alloc(N);
             dtN.alloc(N);
             dR.alloc(N);
-            k_cpq_colsum<real><<<grid_for(N), kBlock, 0, s>>>(N, V, pA, drA0.p);
+            if (sparse) sp.colsum(1, nullptr, nullptr, drA0.p, s);
+            else k_cpq_colsum<real><<<grid_for(N), kBlock, 0, s>>>(N, V, pA, drA0.p);
             k_cpq_init_products<real><<<grid_for(N), kBlock, 0, s>>>(N, drA0.p, dY.p, dtN.p,
                                                                     dR.p);
             PFDR_HIP(hipGetLastError());
@@ -282,7 +286,9 @@ struct QuadDriver : CpDriverBase {
 
     // component column sums (and, preAt, the reduced normal equations) of pfdr_cp_reduce
     void reduce(int preAt, real *rA, real *rAA, real *rY, real *L) {
-        if (sizeof(real) == 4)
+        if (sp.nnz)
+            CP_ABI(cp_reduce_sparse<real>(sp, dY.p, rV, drVc.p, dVc.p, preAt, rA, rAA, rY, L));
+        else if (sizeof(real) == 4)
             CP_ABI(pfdr_cp_reduce_f32(N, V, (const float *)pA, (const float *)dY.p, rV, drVc.p,
                                       dVc.p, preAt, PFDR_MEM_DEVICE, 1e-3f, 100, 10, (float *)rA,
                                       (float *)rAA, (float *)rY, (float *)L, nullptr));
@@ -398,8 +404,11 @@ struct QuadDriver : CpDriverBase {
             if (it == CP_itMax || dif < difTol2) break;
             // steepest cuts (l1 :337-556 / bounds :331-529)
             t = clock::now();
-            CP_ABI(pfdr_cpgraph_gradient(g, N, pA, dY.p, N > 0 ? dR.p : nullptr, PFDR_MEM_DEVICE,
-                                         nullptr));
+            if (sp.nnz)
+                CP_ABI(cpgraph_gradient_sparse(g, &sp, dR.p));
+            else
+                CP_ABI(pfdr_cpgraph_gradient(g, N, pA, dY.p, N > 0 ? dR.p : nullptr,
+                                             PFDR_MEM_DEVICE, nullptr));
             st.gradient += since(t);
             t = clock::now();
             int w = 0, n = 0;

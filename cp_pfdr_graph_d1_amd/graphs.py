@@ -90,6 +90,30 @@ def grid_graph(shape, conn):
     return Eu[ok].astype(np.int32), Ev[ok].astype(np.int32)
 
 
+def blur3x3_csc(nx, ny):
+    """The 3x3 normalised blur on the nx-by-ny grid (grid_graph's vertex
+    order, x fastest; N = V = nx ny, every row sums to 1, up to 9 entries per
+    row and per column) in CSC: (colptr int64[V + 1], rowidx int32[nnz], val
+    float64[nnz]), rows ascending inside each column."""
+    nx, ny = int(nx), int(ny)
+    V = nx * ny
+    v = np.arange(V, dtype=np.int64)
+    x, y = v % nx, v // nx
+    inside = lambda xx, yy: (xx >= 0) & (xx < nx) & (yy >= 0) & (yy < ny)
+    rows, ok = [], []
+    for dy in (-1, 0, 1):      # the neighbours of column v, ascending in vertex id
+        for dx in (-1, 0, 1):
+            rows.append(v + dx + nx * dy)
+            ok.append(inside(x + dx, y + dy))
+    rows, ok = np.stack(rows, 1), np.stack(ok, 1)
+    # entry (i, v) = 1 / (pixels under the mask centred on i)
+    count = ((1 + (x > 0) + (x < nx - 1)) * (1 + (y > 0) + (y < ny - 1))).astype(np.float64)
+    colptr = np.zeros(V + 1, np.int64)
+    np.cumsum(ok.sum(1), out=colptr[1:])
+    rowidx = rows[ok]
+    return colptr, rowidx.astype(np.int32), 1.0 / count[rowidx]
+
+
 def _nbr26():
     offs = []
     for dz in (-1, 0, 1):

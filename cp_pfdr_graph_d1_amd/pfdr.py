@@ -47,10 +47,12 @@ EXPORTED = (
     "pfdr_sequential_sum_f32", "pfdr_sequential_sum_f64",
     "pfdr_radix_sort_pairs_u32", "pfdr_radix_sort_pairs_u64",
     "pfdr_cp_reduce_f32", "pfdr_cp_reduce_f64",
+    "pfdr_cp_reduce_csc_f32", "pfdr_cp_reduce_csc_f64",
     "pfdr_cpgraph_create", "pfdr_cpgraph_destroy", "pfdr_cpgraph_set_active",
     "pfdr_cpgraph_get_active", "pfdr_cpgraph_set_components", "pfdr_cpgraph_get_components",
     "pfdr_cpgraph_set_values", "pfdr_cpgraph_components", "pfdr_cpgraph_reduced_graph",
     "pfdr_cpgraph_get_reduced", "pfdr_cpgraph_merge", "pfdr_cpgraph_gradient",
+    "pfdr_cpgraph_gradient_csc",
     "pfdr_cpgraph_capacities", "pfdr_cpgraph_capacities_bounds", "pfdr_cpgraph_activate",
     "pfdr_cpgraph_simplex_setup", "pfdr_cpgraph_simplex_observations",
     "pfdr_cpgraph_simplex_set_values", "pfdr_cpgraph_simplex_gradient",
@@ -65,7 +67,8 @@ EXPORTED = (
     "pfdr_cp_loss_d1_simplex_stats",
     "pfdr_cp_quadratic_d1_bounds_f32", "pfdr_cp_quadratic_d1_bounds_f64",
     "pfdr_cp_quadratic_d1_bounds_stats",
-    "pfdr_cp_solver_create", "pfdr_cp_solver_destroy", "pfdr_cp_solver_run",
+    "pfdr_cp_solver_create", "pfdr_cp_solver_create_sparse", "pfdr_cp_solver_destroy",
+    "pfdr_cp_solver_run",
     "pfdr_cp_solver_get_state", "pfdr_cp_solver_set_state", "pfdr_cp_solver_set_partition",
     "pfdr_cp_solver_set_penalties", "pfdr_cp_solver_stats",
     "pfdr_cpgraph_set_weights", "pfdr_cpgraph_set_active_by_labels",
@@ -151,6 +154,9 @@ _LIB = None
 def _solver_argtypes(lib, vp):
     """the resumable solver takes its pointers as integers or ctypes pointers"""
     lib.pfdr_cp_solver_create.argtypes = [C.POINTER(vp), C.POINTER(CPProblem)]
+    if hasattr(lib, "pfdr_cp_solver_create_sparse"):
+        lib.pfdr_cp_solver_create_sparse.argtypes = [C.POINTER(vp), C.POINTER(CPProblem),
+                                                     C.POINTER(CSCStruct)]
     lib.pfdr_cp_solver_destroy.argtypes = [vp]
     lib.pfdr_cp_solver_destroy.restype = None
     lib.pfdr_cp_solver_run.argtypes = [vp, C.POINTER(CPParams), vp, vp, vp, vp]
@@ -495,11 +501,17 @@ class Lib:
 
     # the resumable solver (pfdr_cp_solver_*): thin mirrors, pointers as integers
     # or ctypes pointers; CPSolver below is the array-level face
-    def cp_solver_create(self, problem):
-        """pfdr_cp_solver_create(CPProblem) -> handle"""
+    def cp_solver_create(self, problem, csc=None):
+        """pfdr_cp_solver_create(CPProblem), or pfdr_cp_solver_create_sparse
+        with a CSCStruct (or None for its NULL) as well -> handle"""
         h = C.c_void_p()
-        _check(self.lib.pfdr_cp_solver_create(C.byref(h), C.byref(problem)),
-               "pfdr_cp_solver_create")
+        if csc is None:
+            _check(self.lib.pfdr_cp_solver_create(C.byref(h), C.byref(problem)),
+                   "pfdr_cp_solver_create")
+        else:
+            _check(self.lib.pfdr_cp_solver_create_sparse(C.byref(h), C.byref(problem),
+                                                         C.byref(csc)),
+                   "pfdr_cp_solver_create_sparse")
         return h
 
     def cp_solver_destroy(self, handle):
@@ -763,6 +775,22 @@ def CP_PFDR_graph_loss_d1_simplex(Q, al, Eu, Ev, La_d1, CP_difTol, CP_itMax, PFD
     return Cv, rP.reshape((K, rP.size // K), order="F"), it, Time, Obj, Dif
 
 
+def _cp_sparse_run(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho, condMin,
+                   difRcd, difTol, itMax, verbose):
+    """Lib._cp_quadratic for a CSC A: one CPSolver, one run (the solver's first
+    run is defined to equal the one-call entry)"""
+    if flavour == "bounds":
+        kw = dict(lo=own[0], hi=own[1])
+    else:
+        kw = dict(La_l1=own[0], positivity=own[1], duplex=flavour == "duplex")
+    s = CPSolver("bounds" if flavour == "bounds" else "l1", Y, Eu, Ev, La_d1,
+                 A=A.astype(Y.dtype), N=N, **kw)
+    try:
+        return s.run(CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose)
+    finally:
+        s.close()
+
+
 def _cp_front(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho, condMin, difRcd,
               difTol, itMax, verbose, time, obj, dif):
     """the bounds ("bounds", own = Bnd) and duplex ("duplex", own = (La_l1,
@@ -771,10 +799,20 @@ def _cp_front(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho,
     Eu, Ev = _edges(Eu, Ev)
     if flavour == "duplex":
         own = (_scal_or_vec(own[0], V, Y.dtype), own[1])
-    Cv, rX, it, Obj, Dif, Time = Lib()._cp_quadratic(
+    call = _cp_sparse_run if isinstance(A, CSC) else Lib()._cp_quadratic
+    Cv, rX, it, Obj, Dif, Time = call(
         flavour, V, N, Y, A, Eu, Ev, np.asarray(La_d1, Y.dtype), own, CP_difTol, CP_itMax, rho,
         condMin, difRcd, difTol, itMax, verbose)
     return Cv, rX, it, Time if time else None, Obj if obj else None, Dif if dif else None
+
+
+def _cp_matrix(A, dt):
+    """the N-by-V A of a cut-pursuit front end -> (the CSC as it is, or the
+    dense matrix column by column, and its shape)"""
+    if isinstance(A, CSC):
+        return A, A.shape
+    A = np.asarray(A)
+    return np.asfortranarray(A, dt).ravel(order="F"), A.shape
 
 
 def CP_PFDR_graph_quadratic_d1_bounds(Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho,
@@ -782,15 +820,14 @@ def CP_PFDR_graph_quadratic_d1_bounds(Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_it
                                       verbose=0, time=False, obj=False, dif=False):
     """octave/mex/CP_PFDR_graph_quadratic_d1_bounds_mex.cpp: cut pursuit for
     1/2 ||y - A x||^2 + sum_e La_d1 |x_u - x_v| over Bnd[0] <= x <= Bnd[1]
-    (+-inf: no bound), A N-by-V, the whole loop on the GPU
+    (+-inf: no bound), A N-by-V (an array, or a CSC: the same bytes as its
+    densified matrix gives), the whole loop on the GPU
     (pfdr_cp_quadratic_d1_bounds).  Returns (Cv, rX, CP_it, Time, Obj, Dif): the
     component of every vertex (int32[V]), the value of every component -- the
     minimiser is rX[Cv] -- and the records asked for (None otherwise)."""
-    A = np.asarray(A)
     dt = np.result_type(Y, np.float32)
-    N, V = A.shape
-    return _cp_front("bounds", V, N, np.asarray(Y, dt).ravel(),
-                     np.asfortranarray(A, dt).ravel(order="F"), Eu, Ev, La_d1, Bnd, CP_difTol,
+    A, (N, V) = _cp_matrix(A, dt)
+    return _cp_front("bounds", V, N, np.asarray(Y, dt).ravel(), A, Eu, Ev, La_d1, Bnd, CP_difTol,
                      CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
                      verbose, time, obj, dif)
 
@@ -829,16 +866,14 @@ def CP_PFDR_graph_quadratic_d1_l1_duplex(Y, A, Eu, Ev, La_d1, La_l1, positivity,
                                          obj=False, dif=False):
     """octave/mex/CP_PFDR_graph_quadratic_d1_l1_duplex_mex.cpp: cut pursuit for
     1/2 ||y - A x||^2 + sum_e La_d1 |x_u - x_v| + sum_v La_l1 |x_v| (x >= 0 with
-    positivity), A N-by-V, one two-layer cut per iteration, the whole loop on
-    the GPU (pfdr_cp_quadratic_d1_l1_duplex).  La_l1: array, scalar or None.
-    Returns (Cv, rX, CP_it, Time, Obj, Dif): the component of every vertex
+    positivity), A N-by-V (an array or a CSC), one two-layer cut per iteration,
+    the whole loop on the GPU (pfdr_cp_quadratic_d1_l1_duplex).  La_l1: array,
+    scalar or None.  Returns (Cv, rX, CP_it, Time, Obj, Dif): the component of every vertex
     (int32[V]), the value of every component -- the minimiser is rX[Cv] -- and
     the records asked for (None otherwise)."""
-    A = np.asarray(A)
     dt = np.result_type(Y, np.float32)
-    N, V = A.shape
-    return _cp_front("duplex", V, N, np.asarray(Y, dt).ravel(),
-                     np.asfortranarray(A, dt).ravel(order="F"), Eu, Ev, La_d1,
+    A, (N, V) = _cp_matrix(A, dt)
+    return _cp_front("duplex", V, N, np.asarray(Y, dt).ravel(), A, Eu, Ev, La_d1,
                      (La_l1, positivity), CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
                      PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
 
@@ -952,7 +987,8 @@ def _cp_binding(flavour, obs, source, target, edge_weight, A, l1_weight, positiv
     dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
                                                              A, l1_weight)
     if mode == "sparse":
-        raise ValueError("cut pursuit takes a dense A: a CSC is for the PFDR entries")
+        r = _cp_sparse_run(flavour, V, N, obs.ravel(), A, Eu, Ev, ew, (lw, positivity), *args)
+        return r[0].astype(np.uint32), r[1]
     if mode == "identity":
         N, A = 0, None
     elif mode == "diagonal":
@@ -969,7 +1005,8 @@ def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0
     """The reference's Python binding (python/CP_quadratic_l1_py.cpp:68-76,
     188-259): cut pursuit for F(x) = 1/2 ||A x - obs||^2 + sum_e edge_weight
     |x_u - x_v| + sum_v l1_weight |x_v|, same signature, defaults and input
-    conventions (those of PFDR_quadratic_l1), the whole loop on the GPU
+    conventions (those of PFDR_quadratic_l1; a CSC A runs the resumable solver
+    once and gives the bytes of its densified matrix), the whole loop on the GPU
     (pfdr_cp_quadratic_d1_l1).  Returns (Cv, rX): the component of every
     vertex (uint32, as the binding) and the value of every component."""
     return _cp_binding("l1", obs, source, target, edge_weight, A, l1_weight, positivity,
@@ -1297,8 +1334,9 @@ def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normIt
               normNbInit=10):
     """CP reduced-problem builder (pfdr_cp_reduce_*): A is (N, V) for
     N > 0 (or (V, V) A^tA for N < 0, length-V diagonal / None for N = 0),
-    comp_ptr (rV + 1) and comp_vertices (V) the components.  Returns dict
-    rA, rAA, rY, L, Leq (None where not formed)."""
+    comp_ptr (rV + 1) and comp_vertices (V) the components; a CSC A (N > 0)
+    goes through pfdr_cp_reduce_csc_* and gives the bytes of its densified
+    matrix.  Returns dict rA, rAA, rY, L, Leq (None where not formed)."""
     Y = np.asarray(Y)
     dt = Y.dtype
     ct, sfx, _ = _real(dt)
@@ -1306,7 +1344,11 @@ def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normIt
     Vc = np.ascontiguousarray(comp_vertices, np.int32)
     rV, V = ptr.size - 1, Vc.size
     Af = None
-    if A is not None:
+    sparse = isinstance(A, CSC)
+    if sparse:
+        A = A.to_host().astype(dt)
+        csc = A.struct()
+    elif A is not None:
         Af = np.asfortranarray(np.asarray(A, dt)) if np.ndim(A) == 2 else np.ascontiguousarray(A, dt)
     if N <= 0:
         preAt = True
@@ -1316,8 +1358,8 @@ def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normIt
     L = np.zeros(rV, dt)
     Leq = np.zeros(rV, dt) if N != 0 else None
     p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    _check(getattr(load(), "pfdr_cp_reduce_" + sfx)(
-        C.c_int(N), C.c_int(V), p(Af), p(np.ascontiguousarray(Y)), C.c_int(rV), p(ptr), p(Vc),
+    _check(getattr(load(), "pfdr_cp_reduce_" + ("csc_" if sparse else "") + sfx)(
+        C.c_int(N), C.c_int(V), C.byref(csc) if sparse else p(Af), p(np.ascontiguousarray(Y)), C.c_int(rV), p(ptr), p(Vc),
         C.c_int(int(preAt)), PFDR_MEM_HOST, ct(normTol), C.c_int(normItMax),
         C.c_int(normNbInit), p(rA), p(rAA), p(rY), p(L), p(Leq)), "pfdr_cp_reduce")
     return {"rA": None if rA is None else rA.T, "rAA": rAA, "rY": rY, "L": L, "Leq": Leq}
@@ -1406,7 +1448,15 @@ class CPGraph:
         return n.value
 
     def gradient(self, N=0, A=None, Y=None, R=None):
-        """:339-413 -> DfS[V]"""
+        """:339-413 -> DfS[V]; a CSC A (N > 0): pfdr_cpgraph_gradient_csc"""
+        if isinstance(A, CSC):
+            A = A.to_host().astype(self.dtype)
+            R = _arr(R, self.dtype)
+            DfS = np.empty(self.V, self.dtype)
+            csc = A.struct()
+            self._call("pfdr_cpgraph_gradient_csc", C.c_int(N), C.byref(csc), self._p(R),
+                       PFDR_MEM_HOST, self._p(DfS))
+            return DfS
         Af = None
         if A is not None:
             Af = (np.asfortranarray(np.asarray(A, self.dtype)) if np.ndim(A) == 2
@@ -1587,7 +1637,10 @@ class CPSolver:
     the duplex driver.  Y_or_Q, A, N as the one-call entries (Q[V*K] vertex-major
     with K for the simplex).  Every array is a numpy array (host) or a torch
     tensor on the GPU (device pointers; copied by the library, except A, which
-    is borrowed and kept alive here).  The first run() equals the matching
+    is borrowed and kept alive here).  A may be a CSC ("l1" and "bounds", N > 0
+    or taken from it; host, or to_device() with the other arrays on the GPU):
+    it is copied, V is its column count, and every call gives the bytes of the
+    solver on the densified matrix (pfdr_cp_solver_create_sparse).  The first run() equals the matching
     Lib.cp_* call byte for byte; every later one is the reference's warm restart
     from the state the handle holds."""
 
@@ -1617,9 +1670,18 @@ class CPSolver:
         simplex = self.kind == PFDR_KIND_SIMPLEX
         self.K = int(K) if simplex else 1
         self.N = 0 if simplex else int(N)
+        csc = None
+        if isinstance(A, CSC):
+            if A.device != dev:
+                raise TypeError("CPSolver: a CSC on the GPU goes with arrays on the GPU, a host "
+                                "CSC with host arrays")
+            csc, A = A.astype(self.dtype), None
+            self.N = self.N or csc.N
         arrs = [None if a is None else reals(a) for a in (Y_or_Q, A, La_d1, La_l1)]
         Eu, Ev = ints(Eu), ints(Ev)
-        if self.N > 0 and arrs[1] is not None:
+        if csc is not None:
+            self.V = csc.V
+        elif self.N > 0 and arrs[1] is not None:
             self.V = size(arrs[1]) // self.N
         else:
             self.V = size(arrs[0]) // max(self.K, 1)
@@ -1633,7 +1695,7 @@ class CPSolver:
         p.Eu, p.Ev = self._addr(Eu), self._addr(Ev)
         p.positivity, p.min, p.max, p.al = int(positivity), lo, hi, al
         self.has_l1 = La_l1 is not None
-        self._h = self._L.cp_solver_create(p)
+        self._h = self._L.cp_solver_create(p, None if csc is None else csc.struct())
         if not dev:
             self._keep = []
 

@@ -306,7 +306,9 @@ void pfdr_session_destroy(pfdr_session *s);
  * any iteration runs: N <= 0; p->A set as well; the simplex kind; nranks > 1
  * or a communicator; a NULL array; colptr not as above; a row index out of
  * range or not strictly ascending; a column of squared norm 0 (the reference
- * divides by it).  The cut-pursuit entries keep their dense A. */
+ * divides by it).  Cut pursuit takes the same pfdr_csc through
+ * pfdr_cp_solver_create_sparse, pfdr_cp_reduce_csc_* and
+ * pfdr_cpgraph_gradient_csc below. */
 typedef struct pfdr_csc {
     int64_t nnz;
     const int64_t *colptr;
@@ -395,6 +397,26 @@ int pfdr_cp_reduce_f64(int N, int V, const double *A, const double *Y, int rV, c
                        const int *Vc, int preAt, int mem, double normTol, int normItMax,
                        int normNbInit, double *rA, double *rAA, double *rY, double *L,
                        double *Leq);
+/* pfdr_cp_reduce_* for N > 0 with A in CSC (pfdr_csc above; its arrays host
+ * or device per mem, copied in and checked as pfdr_session_create_sparse
+ * checks them, except that a column of squared norm 0 is accepted, as the
+ * dense entry accepts it).  rA stays dense (N-by-rV reals must fit in device
+ * memory; failing that is PFDR_ERR_HIP as for the dense entry): each element
+ * is the sum of the stored entries A[n, Vc[i]] over the component's range of
+ * Vc, i ascending, from +0, which is the dense entry's sum without its +-0
+ * terms.  Every output therefore has the bytes pfdr_cp_reduce_* gives on the
+ * densified matrix, for any partition and either preAt.  No floating atomics:
+ * the same bytes on every run.  N <= 0, a NULL pfdr_csc or array in it, nnz
+ * outside [1, 2^31 - 256): PFDR_ERR_ARG before any device work; a malformed
+ * colptr or rowidx: PFDR_ERR_ARG naming the offence. */
+int pfdr_cp_reduce_csc_f32(int N, int V, const pfdr_csc *A, const float *Y, int rV,
+                           const int *rVc, const int *Vc, int preAt, int mem, float normTol,
+                           int normItMax, int normNbInit, float *rA, float *rAA, float *rY,
+                           float *L, float *Leq);
+int pfdr_cp_reduce_csc_f64(int N, int V, const pfdr_csc *A, const double *Y, int rV,
+                           const int *rVc, const int *Vc, int preAt, int mem, double normTol,
+                           int normItMax, int normNbInit, double *rA, double *rAA, double *rY,
+                           double *L, double *Leq);
 
 /* ------------------------------------------- cut-pursuit graph steps -- */
 /* The full-graph work of every cut-pursuit iteration around the reduced
@@ -438,6 +460,13 @@ int pfdr_cpgraph_merge(pfdr_cpgraph *g, double eps, double CP_difTol, int *deact
  * A = A^tA, Y = A^tY; N = 0: A diagonal or NULL, Y = A^tY */
 int pfdr_cpgraph_gradient(pfdr_cpgraph *g, int N, const void *A, const void *Y,
     const void *R, int mem, void *DfS);
+/* The N > 0 case with A in CSC (val of the graph's real type; A and R host or
+ * device per mem; checked as pfdr_cp_reduce_csc_* checks it): -A^t R adds each
+ * column's products val[e] R[rowidx[e]] in stored order, the dense call's sum
+ * without its +-0 terms, so DfS has the dense call's bytes on the densified
+ * matrix while R is finite. */
+int pfdr_cpgraph_gradient_csc(pfdr_cpgraph *g, int N, const pfdr_csc *A, const void *R,
+    int mem, void *DfS);
 /* cut 0: the single cut of the differentiable case (La_l1 NULL, no
  * positivity); 1 / 2: directions +1_U / -1_U (:402-535).  tr_cap[V]
  * (source > 0 / sink < 0), r_cap[E] (both arcs of an edge), from the
@@ -724,6 +753,23 @@ typedef struct pfdr_cp_solver pfdr_cp_solver;
 
 /* Argument errors are the matching entry's, before any device work. */
 int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem *p);
+/* The same with the observation operator A (p->N-by-p->V, p->N > 0) in CSC;
+ * kinds PFDR_KIND_L1 (duplex or not) and PFDR_KIND_BOUNDS.  A's arrays are
+ * host or device per p->mem and are copied (the dense p->A is borrowed).  Cut
+ * pursuit reads the full-size A in three places -- initialize()'s column sum,
+ * pfdr_cp_reduce's component column sums and the gradient -A^t R -- and those
+ * walk the stored entries in the dense loops' order; the reduced matrix stays
+ * dense (p->N * rV reals) and the rest of the loop is the dense solver's code.
+ * Every run, state and statistic therefore equals, byte for byte, those of
+ * pfdr_cp_solver_create on the densified matrix, and every other
+ * pfdr_cp_solver_* call works on the handle unchanged.  PFDR_ERR_ARG before
+ * any device work: p->N <= 0; p->A set as well; the simplex kind; a NULL A or
+ * array in it; nnz outside [1, 2^31 - 256).  A malformed colptr or rowidx
+ * (as for pfdr_session_create_sparse; a column of squared norm 0 is accepted,
+ * as the dense solver accepts it) is PFDR_ERR_ARG naming the offence, and no
+ * handle is created. */
+int pfdr_cp_solver_create_sparse(pfdr_cp_solver **out, const pfdr_cp_problem *p,
+                                 const pfdr_csc *A);
 void pfdr_cp_solver_destroy(pfdr_cp_solver *s);
 /* Host outputs, any may be NULL: Time[CP_itMax + 1], Obj[CP_itMax + 1],
  * Dif[CP_itMax] of the solver's real type. */
