@@ -99,6 +99,10 @@ class IterLoop : public SessionBase {
         ctrl_.alloc(1);
         static_assert(sizeof(Ctrl<real>) <= kPinnedSmall, "control block");
         hctrl_ = static_cast<Ctrl<real> *>(pinned_small_get());
+        return reset_ctrl();
+    }
+    // the mirror back at iteration 0 (a reload; no copy of it in flight)
+    Ctrl<real> *reset_ctrl() {
         std::memset(hctrl_, 0, sizeof(Ctrl<real>));
         hctrl_->obj_it = -1;
         hctrl_->itMax = itMax_;
@@ -302,6 +306,7 @@ bool IterLoop<real>::settle(bool gated, bool drain) {
     } else if (gated && hctrl_->recond) {
         if (drain) wait_stream();
         recondition();
+        reconditionings++;
         hctrl_->recond = 0;
         hctrl_->halt = 0;
         push_ctrl();

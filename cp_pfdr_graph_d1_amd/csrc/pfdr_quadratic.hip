@@ -97,7 +97,9 @@ __global__ void k_remap_push(long n, long E, const unsigned *__restrict__ inv,
 template <typename real>
 class QuadSession final : public IterLoop<real> {
   public:
-    explicit QuadSession(const pfdr_problem *p, const pfdr_csc *csc = nullptr);
+    explicit QuadSession(const pfdr_problem *p, const pfdr_csc *csc = nullptr,
+                         bool reusable = false);
+    void reload(const pfdr_reload *r) override;
     ~QuadSession() override {
         this->close();  // (the loop's streams are drained before any buffer goes)
         for (hipEvent_t e : ev_) if (e) (void)hipEventDestroy(e);
@@ -117,6 +119,41 @@ class QuadSession final : public IterLoop<real> {
     using L::stopped_, L::chunk_, L::tiny_, L::graphs_ok_, L::capturable_, L::kSpecMax;
     using L::spec_, L::sd_, L::seqdif_, L::chain_, L::route_, L::dws_, L::red_;
     using L::push_ctrl, L::drop_graphs, L::evolution_sum;
+    using L::reusable, L::staging_bytes, L::reconditionings, L::it0_, L::next_print_;
+    // The values of a problem, in the caller's order (host or device per
+    // mem): everything a reload may replace.  load_values() brings them into
+    // the session's order and starts the solve at iteration 0 -- the
+    // constructor's and pfdr_session_reload's one path; finish_values() then
+    // fills what the loop variant keeps beside the iterate.
+    struct Values { int mem; const void *X, *Y, *La_d1, *La_l1, *L; };
+    void set_params(double rho, double condMin, double difRcd, double difTol, double mn,
+                    double mx);
+    void load_values(const Values &in);
+    void finish_values();
+    // a caller's array where the load passes read it: device arrays as they
+    // are, host arrays copied into the session's own buffer (no map) or
+    // staged (st)
+    const real *device_source(DevBuf<real> &st, const void *src, size_t n, int mem, real *dst,
+                              bool mapped);
+    bool reusable_ = false;
+    int itMax0_ = 0;          // the creation's itMax (the records' size)
+    bool rcd_zero_ = false;   // the creation's difRcd == 0
+    bool rcd0_ = false;       // and its square in `real` == 0 (speculative sessions)
+    int it_prev_ = 0;         // load_values: the iteration whose buffer a null X keeps
+    bool has_l1_ = false;     // created with La_l1 (l1 kind)
+    bool tracked(real difRcd, real difTol) const {
+        return difTol > real(0) || difRcd > real(0) || rec_dif_;
+    }
+    bool hasL_ = false;       // created with L
+    real L0_ = real(1);       // a scalar L
+    DevBuf<real> stg_e_, stg_v_[4];  // staged La_d1; Y, La_l1, L, X
+    DevBuf<int> flags_;       // the load passes' verdicts (VF_*)
+    int64_t rr_counted_ = 0;  // rr_'s bytes within device_bytes
+    int64_t stage_bytes() const {
+        size_t n = stg_e_.n;
+        for (const DevBuf<real> &b : stg_v_) n += b.n;
+        return (int64_t)(n * sizeof(real));
+    }
     // problem
     int flavour_;  // 0 l1, 1 bounds
     int V_, Vg_, N_, mode_;
@@ -140,7 +177,7 @@ class QuadSession final : public IterLoop<real> {
     // (cache-served) u-end gathers they replace.
     bool us_ = true;
     DevBuf<char> mono_ws_;       // mono_sum scratch (tile summaries)
-    // uniform La_d1 (k_uniform_check at setup): the iteration kernels take
+    // uniform La_d1 (k_load_edge's verdict): the iteration kernels take
     // the one value la0_ instead of streaming the array (4 B per edge)
     bool la_uniform_ = false;
     real la0_ = real(0);
@@ -168,7 +205,8 @@ class QuadSession final : public IterLoop<real> {
     void spec_decide(int b, hipStream_t s) override;
     static constexpr long kSeqDifMin = 1L << 17;  // AUTO: sums of at least this many terms
     // internal relabelling (pfdr_order.hpp): order_[new] = old, where_[old] = new,
-    // emap_[edge position] = original edge id (setup only)
+    // emap_[edge position] = original edge id (both maps: the value loads; a
+    // reusable session keeps them)
     bool reordered_ = false;
     DevBuf<int> order_, where_, emap_;
     DevBuf<unsigned> eorig_;
@@ -320,12 +358,13 @@ class QuadSession final : public IterLoop<real> {
     // sparse A on its sequential kernels; direct mode, weights >= 0) sum the
     // recorded objective in that order too (k_obj_terms, three mono_sum's):
     // Obj is then the reference's, bit for bit, like X, it and Dif.
-    // oterms_ = the terms of the N rows, E edges (caller's edge order: oemap_
-    // keeps a tiled session's edge positions) and V vertices, each part
-    // 16-byte aligned.
+    // oterms_ = the terms of the N rows, E edges (caller's edge order: a
+    // tiled session keeps emap_, its edge positions, for it) and V vertices,
+    // each part 16-byte aligned.
     bool seqobj_ = false;
     DevBuf<real> oterms_;
-    DevBuf<int> oemap_;
+    bool keep_oemap() const { return sparse_ && rec_obj_; }
+    const int *oemap() const { return keep_oemap() ? emap_.p : nullptr; }
     DevBuf<char> ows_;
     long ot_e_ = 0, ot_v_ = 0;  // offsets of the edge and vertex terms
   public:
@@ -342,10 +381,15 @@ class QuadSession final : public IterLoop<real> {
 
 // ----------------------------------------------------------------- setup --
 template <typename real>
-QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
+QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool reusable_session) {
     if (p->V <= 0 || p->E < 0) throw std::runtime_error("V must be > 0 and E >= 0");
     if (!p->X || !p->Y || !p->Eu || !p->Ev || !p->La_d1)
         throw std::runtime_error("X, Y, Eu, Ev and La_d1 are required");
+    if (reusable_session && (p->nranks > 1 || p->comm))
+        throw std::runtime_error("a reusable session is for one GPU (no partition, no "
+                                 "communicator)");
+    reusable_ = reusable_session;
+    reusable = reusable_ ? 1 : 0;
     PFDR_HIP(hipGetDevice(&device));
     stream = lib_stream();
     pins_.set_stream(stream);
@@ -372,33 +416,22 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
     }
     if (mode_ == A_DIRECT && !p->A && !sparse_) throw std::runtime_error("N > 0 requires A");
     if (mode_ == A_ATA && !p->A) throw std::runtime_error("N < 0 requires A = A^tA");
-    rho_ = (real)p->rho;
-    condMin_ = (real)p->condMin;
-    difTol_ = (real)p->difTol;
-    const real difRcd = (real)p->difRcd;
-    difRcd2_ = difRcd * difRcd;
+    itMax0_ = itMax_;
     rec_obj_ = p->record_obj != 0;
     rec_dif_ = p->record_dif != 0;
-    track_ = (difTol_ > real(0)) || (difRcd > real(0)) || rec_dif_;
+    positivity_ = flavour_ == 0 && p->positivity != 0;
+    has_l1_ = flavour_ == 0 && p->La_l1;
+    set_params(p->rho, p->condMin, p->difRcd, p->difTol, p->min, p->max);
+    track_ = tracked((real)p->difRcd, (real)p->difTol);
+    rcd_zero_ = p->difRcd == 0.0;
+    rcd0_ = difRcd2_ == real(0);
     evo_ = p->evolution;
     if (evo_ < PFDR_EVOLUTION_AUTO || evo_ > PFDR_EVOLUTION_TREE)
         throw std::runtime_error("evolution must be PFDR_EVOLUTION_AUTO, _SEQUENTIAL or _TREE");
     const bool want_seq = track_ && evo_ == PFDR_EVOLUTION_SEQUENTIAL;
     Ldiag_ = (p->Ltype == PFDR_LIPSCHITZ_DIAG) && p->L;
+    hasL_ = p->L != nullptr;
     us_ = E_ >= 4L * V_ || E_ < (1L << 22);
-    // prox selection (ref l1 :499-512, bounds :472-490)
-    positivity_ = 0;
-    lo_ = hi_ = real(0);
-    if (flavour_ == 0) {
-        positivity_ = p->positivity != 0;
-        prox_ = p->La_l1 ? PROX_L1 : (positivity_ ? PROX_POS : PROX_NONE);
-    } else {
-        lo_ = (real)p->min;
-        hi_ = (real)p->max;
-        const real inf = Lim<real>::huge;
-        const bool haslo = -inf < lo_, hashi = hi_ < inf;
-        prox_ = (haslo && hashi) ? PROX_BOX : haslo ? PROX_LO : hashi ? PROX_HI : PROX_NONE;
-    }
 
     // small single-GPU graphs iterate in one 1024-lane workgroup
     // (k_tiny_iterate, four vertex blocks at a time): against the two-launch
@@ -435,9 +468,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
     }
     const int mem = p->mem;
     const size_t V = V_, E = E_, Vg = Vg_;
-    copy_in(La_d1_, p->La_d1, E, mem, s, pins_);
-    if (flavour_ == 0) copy_in(La_l1_, p->La_l1, V, mem, s, pins_);
-    copy_in(Y_, p->Y, mode_ == A_DIRECT ? (size_t)N_ : V, mem, s, pins_);
+    // the matrix and what depends on it alone: kept by a reload
     const size_t asz = sparse_ ? 0 : mode_ == A_DIRECT ? (size_t)N_ * V
                      : mode_ == A_ATA ? (size_t)Vglob_ * V : mode_ == A_DIAG ? V : 0;
     copy_in(A_, p->A, asz, mem, s, pins_);
@@ -449,42 +480,19 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
         sparse_seg_row = sp_.gr;
         sparse_csr_us = (int64_t)(sp_.csr_ms * 1e3);
     }
-    if (emap_.p) {  // edge weights into the internal edge order
-        permute(La_d1_, emap_.p, E, s);
-        if (sparse_ && rec_obj_) {  // (the objective's TV sum runs in the caller's edge order)
-            std::swap(oemap_.p, emap_.p);
-            std::swap(oemap_.n, emap_.n);
-        }
-        emap_.release();
-    }
-    if (reordered_) {  // inputs into the internal labels (identity / diagonal A only)
-        permute(La_l1_, order_.p, V, s);
-        permute(Y_, order_.p, V, s);
+    if (reordered_) {  // into the internal labels (identity / diagonal A only)
         permute(A_, order_.p, V, s);
         amp_orig_.alloc(V);
     }
-    // scalar cap of the metric (ref :225-229), in `real` arithmetic like the reference
-    real cap = real(1.9) * (real(2) - rho_);
-    if (p->L && !Ldiag_) {
-        real L0;
-        PFDR_HIP(hipMemcpyAsync(&L0, p->L, sizeof(real),
-                                mem == PFDR_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-        cap /= L0;
-    }
-    cap_ = cap;
-    if (Ldiag_) copy_in(L_, p->L, V, mem, s, pins_);
-    if (reordered_ && Ldiag_) permute(L_, order_.p, V, s);
-    {   // iterate (X, P) pairs, owned then ghost vertices
-        DevBuf<real> X0;
-        copy_in(X0, p->X, V, mem, s, pins_);
-        if (reordered_) permute(X0, order_.p, V, s);
-        xp_.alloc(Vg + 2);  // (+2: the tiled edge sweep stages vertex pairs, k_edge_sweep_tl)
-        PFDR_HIP(hipMemsetAsync(xp_.p, 0, (Vg + 2) * sizeof(R2<real>), s));
-        k_xp_init<real><<<grid_for(V), kBlock, 0, s>>>(V_, X0.p, xp_.p);
-        PFDR_HIP(hipGetLastError());
-        pull(xp_.p, sizeof(R2<real>));
-    }  // X0 goes back to the device cache (reused once the stream is idle)
+    // the session's copies of the values (load_values fills them), the
+    // iterate's (X, P) pairs, owned then ghost vertices
+    if (E) La_d1_.alloc(E);
+    if (has_l1_) La_l1_.alloc(V);
+    Y_.alloc(mode_ == A_DIRECT ? (size_t)N_ : V);
+    if (Ldiag_) L_.alloc(V);
+    xp_.alloc(Vg + 2);  // (+2: the tiled edge sweep stages vertex pairs, k_edge_sweep_tl)
+    PFDR_HIP(hipMemsetAsync(xp_.p, 0, (Vg + 2) * sizeof(R2<real>), s));
+    flags_.alloc(4);
     // edge state and per-vertex metric
     const size_t En = E ? E : 1;
     // (tiled partitioned ranks: Z's received tail after the 2E local entries,
@@ -519,14 +527,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
     if (mode_ == A_ATA) { pre_.alloc(V); xout_.alloc(V); xfull_.alloc(Vglob_); plan_symv(); }
     if (mode_ == A_DIRECT && halo_) Rsum_.alloc(N_);
 
-    // control block
     this->alloc_ctrl();
-    const real difTol2 = difTol_ * difTol_;
-    hctrl_->dif = difTol2 > difRcd2_ ? difTol2 : difRcd2_;  // ref :342
-    hctrl_->difTol = difTol2;
-    hctrl_->difRcd = difRcd2_;
-    hctrl_->eps = (real(0) < difTol_ && difTol_ < Lim<real>::eps) ? difTol_ : Lim<real>::eps;
-    push_ctrl();
 
     // diagonal of A^t A
     if (mode_ == A_DIRECT) {
@@ -550,58 +551,8 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
         k_diag<real><<<grid_for(V), kBlock, 0, s>>>(V_, mode_, A_.p, Vglob_, v0_, diag_.p);
     }
     PFDR_HIP(hipGetLastError());
-    // uniform La_d1 / La_l1? (read back with c below)
-    DevBuf<int> ubad(2);
-    PFDR_HIP(hipMemsetAsync(ubad.p, 0, 2 * sizeof(int), s));
-    if (E_) k_uniform_check<real><<<grid_for(E), kBlock, 0, s>>>(E_, La_d1_.p, ubad.p);
-    if (La_l1_.p) k_uniform_check<real><<<grid_for(V), kBlock, 0, s>>>(V_, La_l1_.p, ubad.p + 1);
-    // Z = X at both ends, first preconditioning, first forward step
     zs_ = tiled_ ? E_ : 0;
-    if (E_) k_z_init<real><<<grid_for(E), kBlock, 0, s>>>(E_, Eu_.p, Ev_.p, xp_.p, Z2_.p, zs_);
-    precondition(true);
-    if (mode_ == A_IDENT || mode_ == A_DIAG) {
-        grad_.alloc(V);
-        k_grad_vertex<real><<<grid_for(V), kBlock, 0, s>>>(V_, mode_, A_.p, Y_.p, xp_.p, grad_.p);
-        k_forward_grad<real><<<grid_for(V), kBlock, 0, s>>>(V_, Ga_.p, grad_.p, xp_.p);
-        PFDR_HIP(hipGetLastError());
-        grad_.release();
-    } else {
-        forward_dense(GATE_NONE);
-    }
-    if (rec_obj_ && mode_ == A_DIRECT && !halo_ && (exact_ || (sparse_ && sp_.exact))) {
-        DevBuf<int> neg(1);
-        PFDR_HIP(hipMemsetAsync(neg.p, 0, sizeof(int), s));
-        if (E_) k_negative_check<real><<<grid_for(E), kBlock, 0, s>>>(E_, La_d1_.p, neg.p);
-        if (La_l1_.p) k_negative_check<real><<<grid_for(V), kBlock, 0, s>>>(V_, La_l1_.p, neg.p);
-        PFDR_HIP(hipGetLastError());
-        int bad = 1;
-        PFDR_HIP(hipMemcpyAsync(&bad, neg.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-        seqobj_ = bad == 0;
-        if (seqobj_) {
-            ot_e_ = ((long)N_ + 3) / 4 * 4;
-            ot_v_ = ot_e_ + (E_ + 3) / 4 * 4;
-            oterms_.alloc((size_t)ot_v_ + V);
-            ows_.alloc(mono_ws_bytes<real>(std::max<long>(std::max<long>(N_, E_), V_)));
-        }
-    }
-    if (rec_obj_) objective();  // Obj[0]
-    PFDR_HIP(hipStreamSynchronize(s));
-    // c of the first conditioning: a_e = cw_ La_d1[e] in the edge sweeps
-    PFDR_HIP(hipMemcpy(&cw_, &ctrl_.p->c, sizeof(real), hipMemcpyDeviceToHost));
-    if (E_) {
-        int bad = 1;
-        PFDR_HIP(hipMemcpy(&bad, ubad.p, sizeof(int), hipMemcpyDeviceToHost));
-        PFDR_HIP(hipMemcpy(&la0_, La_d1_.p, sizeof(real), hipMemcpyDeviceToHost));
-        la_uniform_ = bad == 0;
-        la_uniform = la_uniform_ ? 1 : 0;
-    }
-    if (La_l1_.p) {
-        int bad = 1;
-        PFDR_HIP(hipMemcpy(&bad, ubad.p + 1, sizeof(int), hipMemcpyDeviceToHost));
-        PFDR_HIP(hipMemcpy(&l1u_, La_l1_.p, sizeof(real), hipMemcpyDeviceToHost));
-        l1_uniform_ = bad == 0;
-    }
+    load_values(Values{p->mem, p->X, p->Y, p->La_d1, p->La_l1, p->L});
     if (halo_) {  // Z-direct on every rank or on none (see zdirect)
         Transport &tr = *halo_->tr;
         DevBuf<real> l0(1);
@@ -619,8 +570,6 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
         tr.wait(s);
         zd_ranks_ = all == 0;
     }
-    pins_.release();
-    stopped_ = (itMax_ <= 0);
     interior_edges = E_;
 
     device_bytes = 0;
@@ -688,11 +637,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
             DevBuf<real> p2((size_t)sd_ * 2 * nbv_);  // and their block sums
             std::swap(vpart_.p, p2.p);
             std::swap(vpart_.n, p2.n);
-            for (int k = 0; k + 1 < sd_; k++) {
-                xpx_[k].alloc(Vg_ + 2);  // (+2 as xp_)
-                PFDR_HIP(hipMemcpyAsync(xpx_[k].p, xp_.p, sizeof(R2<real>) * (Vg_ + 2),
-                                        hipMemcpyDeviceToDevice, s));
-            }
+            for (int k = 0; k + 1 < sd_; k++) xpx_[k].alloc(Vg_ + 2);  // (+2 as xp_)
         }
     }
     {
@@ -704,21 +649,239 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc) {
         const char *e = getenv("PFDR_EDGE_RATIO");
         rat_on_ = e && *e ? e[0] != '0' : speculative != 1;
     }
-    if (rat()) {  // cw_ and la0_ are known from here (owned and ghost ends)
-        rr_.alloc(Vg_ + 2);  // (+2: the tiled edge sweep stages vertex pairs)
-        PFDR_HIP(hipMemsetAsync(rr_.p, 0, (Vg_ + 2) * sizeof(real), s));
-        k_ratio_vertex<real><<<grid_for(Vg_), kBlock, 0, s>>>(Vg_, cw_, la0_, Ga_.p, invAux_.p,
-                                                              rr_.p);
-        PFDR_HIP(hipGetLastError());
-        device_bytes += (int64_t)(rr_.n * sizeof(real));
-        edge_ratio = 1;
+    // the inputs are in the internal order now: only a reusable session
+    // needs the maps again (the sequential evolution of a relabelled session
+    // keeps order_, a sparse session's sequential objective emap_)
+    if ((!seqdif_ || !reordered_) && !reusable_) order_.release();
+    if (!reusable_) {
+        if (!keep_oemap()) emap_.release();
+        stg_e_.release();
+        for (DevBuf<real> &b : stg_v_) b.release();
+    } else {
+        staging_bytes = stage_bytes();
+        acc(emap_.n * 4 + (size_t)staging_bytes);
     }
-    xr_ = xw_ = xp_.p;
-    if (!seqdif_ || !reordered_) order_.release();  // inputs are in the internal labels now
     acc(where_.n * 4 + amp_orig_.n * sizeof(real) + order_.n * 4 + terms_.n * sizeof(real) + dws_.n);
     acc(route_.slice.n * sizeof(real) + route_.chain.ws.n + chain_.ws.n + ampg_.n * sizeof(real) +
         (xpx_[0].n + xpx_[1].n + xpx_[2].n) * sizeof(R2<real>));
     acc(sl_.n * 4 + wzp_.n * sizeof(real) + pidx_.n * 4 + (xpe_.n + gie_.n) * sizeof(R2<real>));
+    finish_values();
+    this->instantiate_setup_graph();
+}
+
+// rho, condMin, the evolution thresholds and the prox (ref l1 :499-512,
+// bounds :472-490) of a problem
+template <typename real>
+void QuadSession<real>::set_params(double rho, double condMin, double difRcd, double difTol,
+                                   double mn, double mx) {
+    rho_ = (real)rho;
+    condMin_ = (real)condMin;
+    difTol_ = (real)difTol;
+    const real rcd = (real)difRcd;
+    difRcd2_ = rcd * rcd;
+    lo_ = hi_ = real(0);
+    if (flavour_ == 0) {
+        prox_ = has_l1_ ? PROX_L1 : (positivity_ ? PROX_POS : PROX_NONE);
+    } else {
+        lo_ = (real)mn;
+        hi_ = (real)mx;
+        const real inf = Lim<real>::huge;
+        const bool haslo = -inf < lo_, hashi = hi_ < inf;
+        prox_ = (haslo && hashi) ? PROX_BOX : haslo ? PROX_LO : hashi ? PROX_HI : PROX_NONE;
+    }
+}
+
+template <typename real>
+const real *QuadSession<real>::device_source(DevBuf<real> &st, const void *src, size_t n, int mem,
+                                             real *dst, bool mapped) {
+    if (!src || !n) return nullptr;
+    if (mem == PFDR_MEM_DEVICE) return static_cast<const real *>(src);
+    if (!mapped && dst) {  // nothing to reorder: straight into the session's copy
+        pins_.copy(dst, src, n * sizeof(real), hipMemcpyHostToDevice);
+        return nullptr;
+    }
+    if (st.n < n) st.alloc(n);
+    pins_.copy(st.p, src, n * sizeof(real), hipMemcpyHostToDevice);
+    return st.p;
+}
+
+// The values `in` (null: the session's own) into the internal order and the
+// solve at iteration 0: the control block, the iterate and Z = X at both
+// ends, the weights' uniformity, the first preconditioning and forward
+// step, Obj[0].  What depends on the graph or on A alone is not touched.
+template <typename real>
+void QuadSession<real>::load_values(const Values &in) {
+    hipStream_t s = stream;
+    const size_t V = V_, E = E_;
+    const int mem = in.mem;
+    it_ = it0_ = next_print_ = 0;
+    reconditionings = 0;
+    stopped_ = (itMax_ <= 0);
+    // control block
+    this->reset_ctrl();
+    const real difTol2 = difTol_ * difTol_;
+    hctrl_->dif = difTol2 > difRcd2_ ? difTol2 : difRcd2_;  // ref :342
+    hctrl_->difTol = difTol2;
+    hctrl_->difRcd = difRcd2_;
+    hctrl_->eps = (real(0) < difTol_ && difTol_ < Lim<real>::eps) ? difTol_ : Lim<real>::eps;
+    push_ctrl();
+    // scalar cap of the metric (ref :225-229), in `real` arithmetic like the reference
+    real cap = real(1.9) * (real(2) - rho_);
+    if (hasL_ && !Ldiag_) {
+        if (in.L) {
+            PFDR_HIP(hipMemcpyAsync(&L0_, in.L, sizeof(real),
+                                    mem == PFDR_MEM_DEVICE ? hipMemcpyDeviceToHost
+                                                           : hipMemcpyHostToHost, s));
+            PFDR_HIP(hipStreamSynchronize(s));
+        }
+        cap /= L0_;
+    }
+    cap_ = cap;
+    // the arrays into the internal order, the iterate's (X, 0) pairs
+    const int *ord = reordered_ ? order_.p : nullptr;
+    const bool vlen = mode_ != A_DIRECT;  // Y of length V
+    if (!vlen && in.Y) {
+        if (mem == PFDR_MEM_DEVICE)
+            PFDR_HIP(hipMemcpyAsync(Y_.p, in.Y, sizeof(real) * N_, hipMemcpyDeviceToDevice, s));
+        else
+            pins_.copy(Y_.p, in.Y, sizeof(real) * N_, hipMemcpyHostToDevice);
+    }
+    VLoad<real> va{};
+    va.V = V_;
+    va.order = ord;
+    va.Yd = vlen ? Y_.p : nullptr;
+    va.l1d = La_l1_.p;
+    va.Ld = Ldiag_ ? L_.p : nullptr;
+    va.Y = vlen ? device_source(stg_v_[0], in.Y, V, mem, Y_.p, ord != nullptr) : nullptr;
+    va.l1 = La_l1_.p ? device_source(stg_v_[1], in.La_l1, V, mem, La_l1_.p, ord != nullptr)
+                     : nullptr;
+    va.L = Ldiag_ ? device_source(stg_v_[2], in.L, V, mem, L_.p, ord != nullptr) : nullptr;
+    va.X = device_source(stg_v_[3], in.X, V, mem, nullptr, ord != nullptr);
+    va.xcur = xpb(it_prev_);
+    va.xp = xp_.p;
+    va.flags = flags_.p;
+    PFDR_HIP(hipMemsetAsync(flags_.p, 0, 4 * sizeof(int), s));
+    k_load_vertex<real><<<grid_for(V, Vec<real>::kPer16B), kBlock, 0, s>>>(va);
+    PFDR_HIP(hipGetLastError());
+    pull(xp_.p, sizeof(R2<real>));
+    // the edge weights, Z = X at both ends
+    if (E_) {
+        const real *la = device_source(stg_e_, in.La_d1, E, mem, La_d1_.p, emap_.p != nullptr);
+        k_load_edge<real><<<grid_for(E, Vec<real>::kPer16B), kBlock, 0, s>>>(
+            E_, emap_.p, la, La_d1_.p, Eu_.p, Ev_.p, xp_.p, Z2_.p, zs_, flags_.p);
+        PFDR_HIP(hipGetLastError());
+    }
+    // the splitting weights are cw La_d1 again, whatever a reconditioning left
+    A1_.release();
+    // first preconditioning, first forward step
+    precondition(true);
+    if (mode_ == A_IDENT || mode_ == A_DIAG) {
+        if (grad_.n < V) grad_.alloc(V);
+        k_grad_vertex<real><<<grid_for(V), kBlock, 0, s>>>(V_, mode_, A_.p, Y_.p, xp_.p, grad_.p);
+        k_forward_grad<real><<<grid_for(V), kBlock, 0, s>>>(V_, Ga_.p, grad_.p, xp_.p);
+        PFDR_HIP(hipGetLastError());
+        if (!reusable_) grad_.release();
+    } else {
+        forward_dense(GATE_NONE);
+    }
+    int hf[4] = {1, 1, 1, 1};
+    seqobj_ = false;
+    if (rec_obj_ && mode_ == A_DIRECT && !halo_ && (exact_ || (sparse_ && sp_.exact))) {
+        PFDR_HIP(hipMemcpyAsync(hf, flags_.p, sizeof(hf), hipMemcpyDeviceToHost, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+        seqobj_ = !hf[VF_D1_NEG] && !hf[VF_L1_NEG];
+        if (seqobj_ && !oterms_.p) {
+            ot_e_ = ((long)N_ + 3) / 4 * 4;
+            ot_v_ = ot_e_ + (E_ + 3) / 4 * 4;
+            oterms_.alloc((size_t)ot_v_ + V);
+            ows_.alloc(mono_ws_bytes<real>(std::max<long>(std::max<long>(N_, E_), V_)));
+        }
+    }
+    if (rec_obj_) objective();  // Obj[0]
+    PFDR_HIP(hipStreamSynchronize(s));
+    // c of the first conditioning: a_e = cw_ La_d1[e] in the edge sweeps
+    PFDR_HIP(hipMemcpy(&cw_, &ctrl_.p->c, sizeof(real), hipMemcpyDeviceToHost));
+    PFDR_HIP(hipMemcpy(hf, flags_.p, sizeof(hf), hipMemcpyDeviceToHost));
+    if (E_) {
+        PFDR_HIP(hipMemcpy(&la0_, La_d1_.p, sizeof(real), hipMemcpyDeviceToHost));
+        la_uniform_ = hf[VF_D1_VARIES] == 0;
+        la_uniform = la_uniform_ ? 1 : 0;
+    }
+    if (La_l1_.p) {
+        PFDR_HIP(hipMemcpy(&l1u_, La_l1_.p, sizeof(real), hipMemcpyDeviceToHost));
+        l1_uniform_ = hf[VF_L1_VARIES] == 0;
+    }
+    pins_.release();
+    it_prev_ = 0;
+}
+
+// what the session's loop variant keeps beside the iterate: the per-edge
+// endpoint copies of a padded session, the speculative iterate buffers, the
+// formed ratios of the ratio edge sweep (cw_ and la0_ are known here)
+template <typename real>
+void QuadSession<real>::finish_values() {
+    hipStream_t s = stream;
+    refresh_ends();
+    if (spec_)
+        for (int k = 0; k + 1 < sd_; k++)
+            PFDR_HIP(hipMemcpyAsync(xpx_[k].p, xp_.p, sizeof(R2<real>) * (Vg_ + 2),
+                                    hipMemcpyDeviceToDevice, s));
+    if (rat()) {  // (owned and ghost ends)
+        if (!rr_.p) {
+            rr_.alloc(Vg_ + 2);  // (+2: the tiled edge sweep stages vertex pairs)
+            PFDR_HIP(hipMemsetAsync(rr_.p, 0, (Vg_ + 2) * sizeof(real), s));
+        }
+        k_ratio_vertex<real><<<grid_for(Vg_), kBlock, 0, s>>>(Vg_, cw_, la0_, Ga_.p, invAux_.p,
+                                                              rr_.p);
+        PFDR_HIP(hipGetLastError());
+    } else {
+        rr_.release();
+    }
+    edge_ratio = rr_.p ? 1 : 0;
+    device_bytes += (int64_t)(rr_.n * sizeof(real)) - rr_counted_;
+    rr_counted_ = (int64_t)(rr_.n * sizeof(real));
+    xr_ = xw_ = xp_.p;
+}
+
+// pfdr_session_reload: the checks, all before any device work, then the
+// constructor's own load
+template <typename real>
+void QuadSession<real>::reload(const pfdr_reload *r) {
+    if (!reusable_)
+        throw std::runtime_error("the session was not created reusable "
+                                 "(pfdr_session_create_reusable)");
+    if (halo_) throw std::runtime_error("a partitioned session cannot be reloaded");
+    if (r->mem != PFDR_MEM_HOST && r->mem != PFDR_MEM_DEVICE)
+        throw std::runtime_error("mem must be PFDR_MEM_HOST or PFDR_MEM_DEVICE");
+    if (r->La_l1 && !has_l1_)
+        throw std::runtime_error("La_l1 given, but the session was created without it");
+    if (r->L && !hasL_)
+        throw std::runtime_error("L given, but the session was created without it");
+    if (flavour_ == 1 && !(r->min <= r->max))
+        throw std::runtime_error("bounds: min > max or NaN");
+    if (r->itMax > itMax0_)
+        throw std::runtime_error("itMax above the one the session was created with (the "
+                                 "records are sized by it)");
+    const real rcd = (real)r->difRcd, tol = (real)r->difTol;
+    if (tracked(rcd, tol) != track_)
+        throw std::runtime_error("difTol / difRcd would switch the tracking of the iterate "
+                                 "evolution, chosen at creation");
+    if ((r->difRcd == 0.0) != rcd_zero_)
+        throw std::runtime_error("difRcd cannot change between zero and non-zero");
+    if ((rcd * rcd == real(0)) != rcd0_)
+        throw std::runtime_error("difRcd would move the session to another loop variant "
+                                 "(speculative or not), chosen at creation");
+    hipStream_t s = stream;
+    PFDR_HIP(hipStreamSynchronize(s));  // (no control-block copy in flight)
+    it_prev_ = it_;
+    itMax_ = r->itMax;
+    set_params(r->rho, r->condMin, r->difRcd, r->difTol, r->min, r->max);
+    drop_graphs();  // cw_ and la0_ are kernel arguments of the captured bodies
+    if (capturable_) graphs_ok_ = itMax_ >= 2 * chunk_;
+    load_values(Values{r->mem, r->X, r->Y, r->La_d1, r->La_l1, r->L});
+    finish_values();
+    device_bytes += stage_bytes() - staging_bytes;
+    staging_bytes = stage_bytes();
     this->instantiate_setup_graph();
 }
 
@@ -757,8 +920,7 @@ void QuadSession<real>::plan_pad() {
     PFDR_HIP(hipGetLastError());
     pad_nmax_ = nmax;
     pad_ = true;
-    padded = 1;
-    refresh_ends();
+    padded = 1;  // (finish_values fills the endpoint copies)
 }
 
 template <typename real>
@@ -1381,7 +1543,7 @@ void QuadSession<real>::objective() {
         real *tn = oterms_.p, *te = oterms_.p + ot_e_, *tv = oterms_.p + ot_v_;
         const long nmax = std::max<long>(std::max<long>(N_, E_), V_);
         k_obj_terms<real><<<grid_for(nmax), kBlock, 0, s>>>(
-            N_, E_, V_, R_.p, Eu_.p, Ev_.p, oemap_.p, xp_.p, La_d1_.p,
+            N_, E_, V_, R_.p, Eu_.p, Ev_.p, oemap(), xp_.p, La_d1_.p,
             flavour_ == 0 ? La_l1_.p : nullptr, tn, te, tv, c);
         PFDR_HIP(hipGetLastError());
         PFDR_HIP(hipMemsetAsync(red_.p, 0, 3 * sizeof(real), s));
@@ -1771,6 +1933,13 @@ void QuadSession<real>::result(void *X_host, int *it, void *Obj_host, void *Dif_
 SessionBase *create_quadratic_session(const pfdr_problem *p) {
     if (p->dtype == PFDR_F32) return new QuadSession<float>(p);
     if (p->dtype == PFDR_F64) return new QuadSession<double>(p);
+    throw std::runtime_error("dtype must be PFDR_F32 or PFDR_F64");
+}
+
+// pfdr_session_create_reusable: A null for a dense (or no) matrix
+SessionBase *create_quadratic_session_reusable(const pfdr_problem *p, const pfdr_csc *A) {
+    if (p->dtype == PFDR_F32) return new QuadSession<float>(p, A, true);
+    if (p->dtype == PFDR_F64) return new QuadSession<double>(p, A, true);
     throw std::runtime_error("dtype must be PFDR_F32 or PFDR_F64");
 }
 

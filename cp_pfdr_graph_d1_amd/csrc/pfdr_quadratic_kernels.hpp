@@ -909,16 +909,6 @@ static __global__ __launch_bounds__(256) void k_split_build(int V, long E, const
 // ====================================================================== //
 
 template <typename real>
-__global__ void k_xp_init(int V, const real *__restrict__ X, R2<real> *xp) {
-    int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= V) return;
-    R2<real> o;
-    o.x = X[v];
-    o.y = real(0);
-    xp[v] = o;
-}
-
-template <typename real>
 __global__ void k_x_extract(int V, const R2<real> *__restrict__ xp,
                             real *__restrict__ X) {
     int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -953,18 +943,6 @@ __global__ void k_scatter(long n, const T *__restrict__ src, const int *__restri
 // side-major Z[side * zs + e] (zs = E: tile-ordered sessions)
 __device__ __forceinline__ long zat(long e, int side, long zs) {
     return zs ? side * zs + e : 2 * e + side;
-}
-
-// Z_u = X[Eu], Z_v = X[Ev]   (ref :320-324)
-template <typename real>
-__global__ void k_z_init(long E, const int *__restrict__ Eu,
-                         const int *__restrict__ Ev,
-                         const R2<real> *__restrict__ xp,
-                         real *__restrict__ Z2, long zs) {
-    long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    Z2[zat(e, 0, zs)] = xp[Eu[e]].x;
-    Z2[zat(e, 1, zs)] = xp[Ev[e]].x;
 }
 
 // diagonal of A^t A for the identity / diagonal / A^tA modes (ref :101-122)
@@ -1417,7 +1395,7 @@ __device__ __forceinline__ real edge_a(long e, const real *__restrict__ A1,
 }
 
 // La_d1[e] of the iteration kernels: a null array means every edge weighs
-// la0 (a uniform La_d1 detected at setup, k_uniform_check: the 4-byte
+// la0 (a uniform La_d1 detected when the values are loaded, k_load_edge: the 4-byte
 // stream is not read; the value, and so every operation, is the same)
 template <typename real>
 __device__ __forceinline__ real la_at(long e, const real *__restrict__ La_d1, real la0) {
@@ -1434,16 +1412,6 @@ __device__ __forceinline__ Pk<real, N> la_vec(long e0, const real *__restrict__ 
         for (int j = 0; j < N; j++) la.v[j] = x.v[j];
     }
     return la;
-}
-
-// nonzero *bad when some La_d1[e] differs from La_d1[0] (bitwise)
-template <typename real>
-__global__ void k_uniform_check(long E, const real *__restrict__ La_d1, int *__restrict__ bad) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    using U = typename std::conditional<sizeof(real) == 4, unsigned, unsigned long long>::type;
-    const U x = *reinterpret_cast<const U *>(La_d1 + e), x0 = *reinterpret_cast<const U *>(La_d1);
-    if (__any(x != x0) && (threadIdx.x & (kWave - 1)) == 0) atomicOr(bad, 1);
 }
 
 // d1 contributions a_e to the per-vertex sums (both ends through the CSR,
@@ -3114,13 +3082,6 @@ __global__ __launch_bounds__(256) void k_obj_terms(
     }
 }
 
-// flag[0] = 1 when some weight is negative (or NaN): its terms are not mono_sum's
-template <typename real>
-__global__ void k_negative_check(long n, const real *__restrict__ w, int *__restrict__ flag) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && !(w[i] >= real(0))) flag[0] = 1;
-}
-
 // objective partials -> red[0..2] = (data, l1, tv)
 template <typename real>
 __global__ __launch_bounds__(256) void k_obj_reduce(
@@ -3153,6 +3114,153 @@ __global__ void k_obj_write(const real *__restrict__ red3, int direct, int has_l
     const int it = ctrl ? ctrl->it : 0;
     Obj[it] = o;
     if (ctrl) ctrl->obj_it = it;
+}
+
+// ------------------------------------------------- value (re)load passes --
+// The values of a problem into a session's internal order (its creation and
+// pfdr_session_reload): one vertex pass and one edge pass in place of a chain
+// of per-array copies, gathers, checks and initialisations (every stored word
+// is that chain's).  A lane takes the 16 bytes of
+// consecutive internal positions (their sources through the map are
+// scattered 4 / 8-byte reads; a null map streams them in 16 bytes too).
+// flags[4]: La_d1 not uniform, La_l1 not uniform (bitwise against the first
+// internal element), a negative or NaN La_d1, La_l1 (their objective terms are
+// not mono_sum's).
+enum : int { VF_D1_VARIES = 0, VF_L1_VARIES = 1, VF_D1_NEG = 2, VF_L1_NEG = 3 };
+
+template <typename real>
+__device__ __forceinline__ bool bits_differ(real a, real b) {
+    using U = typename std::conditional<sizeof(real) == 4, unsigned, unsigned long long>::type;
+    return __builtin_bit_cast(U, a) != __builtin_bit_cast(U, b);
+}
+
+// N values of internal positions [i0, i0 + N): src through map (null map:
+// src[i0 ..]); a null src reads the session's copy dst in place
+template <typename real, int N>
+__device__ __forceinline__ Pk<real, N> load_mapped(long i0, Pk<int, N> m, bool mapped,
+                                                   const real *src, const real *dst) {
+    if (!src) return ldv<real, N>(dst + i0);
+    if (!mapped) return ldv<real, N>(src + i0);
+    Pk<real, N> x;
+#pragma unroll
+    for (int j = 0; j < N; j++) x.v[j] = src[m.v[j]];
+    return x;
+}
+
+template <typename real>
+struct VLoad {
+    int V;
+    const int *order;             // order[internal] = caller's label (null: the same)
+    const real *Y, *l1, *L, *X;   // the caller's arrays on the device (null: kept)
+    real *Yd, *l1d, *Ld;          // the session's copies (null: the session has none)
+    const R2<real> *xcur;         // the iterate a null X keeps
+    R2<real> *xp;                 // (X, 0) pairs out
+    int *flags;
+};
+
+template <typename real>
+__global__ __launch_bounds__(kBlock) void k_load_vertex(const VLoad<real> a) {
+    constexpr int W = Vec<real>::kPer16B;
+    const long i0 = ((long)blockIdx.x * kBlock + threadIdx.x) * W;
+    const bool mapped = a.order != nullptr;
+    bool varies = false, neg = false;
+    real l10 = real(0);
+    if (a.l1d) l10 = a.l1 ? a.l1[mapped ? a.order[0] : 0] : a.l1d[0];
+    if (i0 + W <= a.V) {
+        Pk<int, W> m{};
+        if (mapped) m = ldv<int, W>(a.order + i0);
+        if (a.Yd && a.Y) stv<real, W>(a.Yd + i0, load_mapped<real, W>(i0, m, mapped, a.Y, a.Yd));
+        if (a.Ld && a.L) stv<real, W>(a.Ld + i0, load_mapped<real, W>(i0, m, mapped, a.L, a.Ld));
+        if (a.l1d) {
+            const Pk<real, W> x = load_mapped<real, W>(i0, m, mapped, a.l1, a.l1d);
+#pragma unroll
+            for (int j = 0; j < W; j++) {
+                varies |= bits_differ(x.v[j], l10);
+                neg |= !(x.v[j] >= real(0));
+            }
+            if (a.l1) stv<real, W>(a.l1d + i0, x);
+        }
+        Pk<real, 2 * W> o;
+        if (a.X) {
+            const Pk<real, W> x = load_mapped<real, W>(i0, m, mapped, a.X, a.X);
+#pragma unroll
+            for (int j = 0; j < W; j++) o.v[2 * j] = x.v[j];
+        } else {
+            o = ldv<real, 2 * W>(reinterpret_cast<const real *>(a.xcur + i0));
+        }
+#pragma unroll
+        for (int j = 0; j < W; j++) o.v[2 * j + 1] = real(0);
+        stv<real, 2 * W>(reinterpret_cast<real *>(a.xp + i0), o);
+    } else {
+        for (long i = i0; i < a.V; i++) {
+            const long q = mapped ? a.order[i] : i;
+            if (a.Yd && a.Y) a.Yd[i] = a.Y[q];
+            if (a.Ld && a.L) a.Ld[i] = a.L[q];
+            if (a.l1d) {
+                const real x = a.l1 ? a.l1[q] : a.l1d[i];
+                varies |= bits_differ(x, l10);
+                neg |= !(x >= real(0));
+                if (a.l1) a.l1d[i] = x;
+            }
+            R2<real> o;
+            o.x = a.X ? a.X[q] : a.xcur[i].x;
+            o.y = real(0);
+            a.xp[i] = o;
+        }
+    }
+    const bool lead = (threadIdx.x & (kWave - 1)) == 0;
+    if (__any(varies) && lead) atomicOr(a.flags + VF_L1_VARIES, 1);
+    if (__any(neg) && lead) atomicOr(a.flags + VF_L1_NEG, 1);
+}
+
+// La_d1 through the edge map, its two checks, and Z = X at both ends of every
+// edge (ref :320-324) in the session's Z layout (zat)
+template <typename real>
+__global__ __launch_bounds__(kBlock) void k_load_edge(
+    long E, const int *__restrict__ emap, const real *__restrict__ la, real *lad,
+    const int *__restrict__ Eu, const int *__restrict__ Ev, const R2<real> *__restrict__ xp,
+    real *__restrict__ Z2, long zs, int *flags) {
+    constexpr int W = Vec<real>::kPer16B;
+    const long e0 = ((long)blockIdx.x * kBlock + threadIdx.x) * W;
+    const bool mapped = emap != nullptr;
+    bool varies = false, neg = false;
+    const real la0 = la ? la[mapped ? emap[0] : 0] : lad[0];
+    if (e0 + W <= E) {
+        Pk<int, W> m{};
+        if (mapped && la) m = ldv<int, W>(emap + e0);
+        const Pk<real, W> x = load_mapped<real, W>(e0, m, mapped, la, lad);
+#pragma unroll
+        for (int j = 0; j < W; j++) {
+            varies |= bits_differ(x.v[j], la0);
+            neg |= !(x.v[j] >= real(0));
+        }
+        if (la) stv<real, W>(lad + e0, x);
+        const Pk<int, W> iu = ldv<int, W>(Eu + e0), iv = ldv<int, W>(Ev + e0);
+        if (zs) {
+            Pk<real, W> zu, zv;
+#pragma unroll
+            for (int j = 0; j < W; j++) { zu.v[j] = xp[iu.v[j]].x; zv.v[j] = xp[iv.v[j]].x; }
+            stv<real, W>(Z2 + e0, zu);
+            stv<real, W>(Z2 + zs + e0, zv);
+        } else {
+            Pk<real, 2 * W> z;
+#pragma unroll
+            for (int j = 0; j < W; j++) { z.v[2 * j] = xp[iu.v[j]].x; z.v[2 * j + 1] = xp[iv.v[j]].x; }
+            stv<real, 2 * W>(Z2 + 2 * e0, z);
+        }
+    } else {
+        for (long e = e0; e < E; e++) {
+            const real x = la ? la[mapped ? emap[e] : e] : lad[e];
+            varies |= bits_differ(x, la0);
+            neg |= !(x >= real(0));
+            if (la) lad[e] = x;
+            Z2[zat(e, 0, zs)] = xp[Eu[e]].x;
+            Z2[zat(e, 1, zs)] = xp[Ev[e]].x;
+        }
+    }
+    const bool lead = (threadIdx.x & (kWave - 1)) == 0;
+    if (__any(varies) && lead) atomicOr(flags + VF_D1_VARIES, 1);
+    if (__any(neg) && lead) atomicOr(flags + VF_D1_NEG, 1);
 }
 
 }  // namespace pfdr

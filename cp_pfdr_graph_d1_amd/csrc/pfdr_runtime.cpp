@@ -363,6 +363,7 @@ bool Profiler::stats(const char *name, int *launches, double *mean_ms) const {
 SessionBase *create_quadratic_session(const pfdr_problem *p);
 SessionBase *create_simplex_session(const pfdr_problem *p);
 SessionBase *create_quadratic_session_sparse(const pfdr_problem *p, const pfdr_csc *A);
+SessionBase *create_quadratic_session_reusable(const pfdr_problem *p, const pfdr_csc *A);
 
 }  // namespace pfdr
 
@@ -410,6 +411,31 @@ extern "C" int pfdr_session_create_sparse(pfdr_session **out, const pfdr_problem
         if (p->kind != PFDR_KIND_L1 && p->kind != PFDR_KIND_BOUNDS)
             return report_error(fn, "sparse A is for the l1 and bounds kinds (not the simplex)");
         *out = new pfdr_session{create_quadratic_session_sparse(p, A)};
+    });
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_session_create_reusable(pfdr_session **out, const pfdr_problem *p,
+                                            const pfdr_csc *A) {
+    const char *fn = "pfdr_session_create_reusable";
+    if (!out || !p) return report_error(fn, "null argument");
+    *out = nullptr;
+    PFDR_GUARD(fn, {
+        if (p->kind == PFDR_KIND_SIMPLEX)
+            return report_error(fn, "the simplex kind has no reusable sessions");
+        if (p->kind != PFDR_KIND_L1 && p->kind != PFDR_KIND_BOUNDS)
+            return report_error(fn, "unknown problem kind");
+        *out = new pfdr_session{create_quadratic_session_reusable(p, A)};
+    });
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_session_reload(pfdr_session *s, const pfdr_reload *r) {
+    const char *fn = "pfdr_session_reload";
+    if (!s || !r) return report_error(fn, "null argument");
+    PFDR_GUARD(fn, {
+        StreamScope sc(s->impl->stream, s->impl->device);
+        s->impl->reload(r);
     });
     return PFDR_OK;
 }
@@ -547,6 +573,9 @@ extern "C" int pfdr_session_query(pfdr_session *s, const char *what, int64_t *va
     else if (!strcmp(what, "sparse_csr_us")) *value = s->impl->sparse_csr_us;
     else if (!strcmp(what, "interior_edges")) *value = s->impl->interior_edges;
     else if (!strcmp(what, "device_bytes")) *value = s->impl->device_bytes;
+    else if (!strcmp(what, "reusable")) *value = s->impl->reusable;
+    else if (!strcmp(what, "staging_bytes")) *value = s->impl->staging_bytes;
+    else if (!strcmp(what, "reconditionings")) *value = s->impl->reconditionings;
     else return report_error("pfdr_session_query", (std::string("unknown key ") + what).c_str());
     return PFDR_OK;
 }

@@ -60,6 +60,14 @@ class SessionBase {
     virtual void *device_x() = 0;
     // capture (once) the graphs a later run(iters) replays; no iteration runs
     virtual void prepare(int iters) { (void)iters; }
+    // new values on the kept graph, back to iteration 0 (reusable quadratic
+    // sessions, pfdr_session_reload)
+    virtual void reload(const pfdr_reload *) {
+        throw std::runtime_error("the simplex kind has no reusable sessions");
+    }
+    int64_t reusable = 0;         // created by pfdr_session_create_reusable
+    int64_t staging_bytes = 0;    // device staging a reusable session keeps for host arrays
+    int64_t reconditionings = 0;  // since the creation or the last reload
     int64_t device_bytes = 0;
     int64_t reordered = 0;  // internal locality relabelling applied
     int64_t split_blocks = 0;  // vertex blocks on the split-incidence path

@@ -2146,7 +2146,7 @@ __global__ void k_sxt_rec(int nb, int V, int vb, int K, int cap, const int *__re
 }
 
 // *bad += the entries of La_d1 that differ from La_d1[0].  (The session's
-// own kernel: the quadratic file's k_uniform_check, launched from here, made
+// own kernel: the quadratic file's uniformity kernel, launched from here, made
 // the runtime load that file's code object, which cost C4 1 %)
 template <typename real>
 __global__ void k_sx_uniform_check(long E, const real *__restrict__ x, int *__restrict__ bad) {

@@ -77,6 +77,7 @@ EXPORTED = (
     "pfdr_session_kernel_stats", "pfdr_session_sync",
     "pfdr_session_device_bytes", "pfdr_session_query", "pfdr_session_destroy",
     "pfdr_session_create_sparse", "pfdr_debug_session_csr",
+    "pfdr_session_create_reusable", "pfdr_session_reload",
     "pfdr_quadratic_d1_l1_csc_f32", "pfdr_quadratic_d1_l1_csc_f64",
     "pfdr_quadratic_d1_bounds_csc_f32", "pfdr_quadratic_d1_bounds_csc_f64",
     "pfdr_comm_unique_id", "pfdr_comm_init", "pfdr_comm_destroy",
@@ -126,6 +127,19 @@ class CSCStruct(C.Structure):
     """Mirror of ``pfdr_csc`` (include/pfdr_mi355x.h)."""
     _fields_ = [("nnz", C.c_int64), ("colptr", C.c_void_p), ("rowidx", C.c_void_p),
                 ("val", C.c_void_p)]
+
+
+class Reload(C.Structure):
+    """Mirror of ``pfdr_reload`` (include/pfdr_mi355x.h)."""
+    _fields_ = [
+        ("mem", C.c_int),
+        ("X", C.c_void_p), ("Y", C.c_void_p), ("La_d1", C.c_void_p), ("La_l1", C.c_void_p),
+        ("L", C.c_void_p),
+        ("min", C.c_double), ("max", C.c_double),
+        ("rho", C.c_double), ("condMin", C.c_double),
+        ("difRcd", C.c_double), ("difTol", C.c_double),
+        ("itMax", C.c_int),
+    ]
 
 
 class CPProblem(C.Structure):
@@ -1063,10 +1077,11 @@ class Session:
                  record_dif=False, verbose=0, device=False, nranks=0, rank=0,
                  comm=None, comm_kind=0, vtx_begin=0, V_global=0, e_global=None,
                  e_offset=0, reorder=REORDER_AUTO, evolution=EVOLUTION_AUTO,
-                 vtx_label=None, spec=SPEC_AUTO):
+                 vtx_label=None, spec=SPEC_AUTO, reusable=False):
         self.lib = load()
         ct, _, dcode = _real(dtype)
         self._keep = []
+        self.device, self.reusable = bool(device), bool(reusable)
         if device:
             _producers_done()
 
@@ -1127,6 +1142,11 @@ class Session:
             if device:
                 _producers_done()  # (the conversions above may have queued copies)
             cs = csc.struct()
+        if reusable:
+            _check(self.lib.pfdr_session_create_reusable(
+                C.byref(h), C.byref(p), None if csc is None else C.byref(cs)),
+                "pfdr_session_create_reusable")
+        elif csc is not None:
             _check(self.lib.pfdr_session_create_sparse(C.byref(h), C.byref(p), C.byref(cs)),
                    "pfdr_session_create_sparse")
         else:
@@ -1158,6 +1178,43 @@ class Session:
     def prepare(self, iters):
         """capture the hipGraphs run(iters) will replay (no iteration runs)"""
         _check(self.lib.pfdr_session_prepare(self.h, C.c_int(int(iters))), "pfdr_session_prepare")
+
+    def reload(self, Y=None, La_d1=None, La_l1=None, X0=None, L=None, lo=None, hi=None,
+               rho=None, condMin=None, difRcd=None, difTol=None, itMax=None):
+        """New values on the kept graph and matrix, back to iteration 0
+        (pfdr_session_reload; the session was created with reusable=True).
+        None keeps the current value; for X0 that is the current iterate (a
+        warm start).  Arrays as at creation: numpy, or torch GPU tensors when
+        the session was created with device=True."""
+        p = self.problem
+        keep = []
+        if self.device:
+            _producers_done()
+
+        def addr(a):
+            if a is None:
+                return None
+            if self.device:
+                keep.append(a)
+                return C.c_void_p(a.data_ptr())
+            a = np.ascontiguousarray(a, self.dtype)
+            keep.append(a)
+            return C.c_void_p(a.ctypes.data)
+
+        def scalar(new, cur):
+            return cur if new is None else new
+
+        r = Reload()
+        r.mem = p.mem
+        r.X, r.Y, r.La_d1, r.La_l1, r.L = addr(X0), addr(Y), addr(La_d1), addr(La_l1), addr(L)
+        r.min, r.max = scalar(lo, p.min), scalar(hi, p.max)
+        r.rho, r.condMin = scalar(rho, p.rho), scalar(condMin, p.condMin)
+        r.difRcd, r.difTol = scalar(difRcd, p.difRcd), scalar(difTol, p.difTol)
+        r.itMax = scalar(itMax, p.itMax)
+        _check(self.lib.pfdr_session_reload(self.h, C.byref(r)), "pfdr_session_reload")
+        # (the call has copied every array; the scalars are the session's now)
+        p.min, p.max, p.rho, p.condMin = r.min, r.max, r.rho, r.condMin
+        p.difRcd, p.difTol, p.itMax = r.difRcd, r.difTol, r.itMax
 
     def profile(self, on=True, period=1, only=None):
         """time kernels with HIP events: every `period`-th launch, of the

@@ -274,7 +274,10 @@ int64_t pfdr_session_device_bytes(pfdr_session *s);
  * "sparse_exact" (1: the four products add the stored entries in the
  * reference's order, bit-exact on the densified matrix; 0: the parallel
  * kernels), "sparse_seg_col" / "sparse_seg_row" (lanes per column / row of
- * the parallel kernels) and "sparse_csr_us" (wall time of the CSR build). */
+ * the parallel kernels) and "sparse_csr_us" (wall time of the CSR build).
+ * "reusable" (1: created by pfdr_session_create_reusable), "staging_bytes"
+ * (the device staging such a session keeps for host arrays) and
+ * "reconditionings" (their count since the creation or the last reload). */
 int pfdr_session_query(pfdr_session *s, const char *what, int64_t *value);
 void pfdr_session_destroy(pfdr_session *s);
 
@@ -342,6 +345,57 @@ int pfdr_quadratic_d1_bounds_csc_f64(int V, int E, int N, double *X, const doubl
 /* Debug: the CSR view a sparse session built (rowptr[N+1], colidx[nnz],
  * rval[nnz] of the session's real type; host arrays, any may be NULL). */
 int pfdr_debug_session_csr(pfdr_session *s, int64_t *rowptr, int32_t *colidx, void *rval);
+
+/* ---------------------------------------------------- reusable sessions -- */
+/* A quadratic session (PFDR_KIND_L1 / _BOUNDS, one GPU) that solves problem
+ * after problem on the graph and the matrix it was created with.
+ * pfdr_session_create_reusable is pfdr_session_create (A NULL) or
+ * pfdr_session_create_sparse (A given) and behaves and runs exactly as they
+ * do; it only keeps what a reload needs and they release: the map from the
+ * internal edge order to the caller's (4 bytes per edge, tile-ordered or
+ * relabelled sessions), the relabelling (4 bytes per vertex, relabelled
+ * sessions) and the device staging of host arrays that go through either.
+ * "device_bytes" counts them ("staging_bytes": the staging alone).  The
+ * simplex kind and partitioned problems (nranks > 1 or a communicator) are
+ * PFDR_ERR_ARG.
+ *
+ * pfdr_session_reload replaces values and restarts the solve at iteration 0,
+ * as if a session had just been created on the new problem: the result of the
+ * runs that follow (X, it, Obj, Dif) and the session's path queries equal a
+ * fresh session's bit for bit.  X, Y, La_d1, La_l1, L: in the caller's vertex
+ * / edge order and the session's real type, host or device memory per mem; a
+ * NULL pointer keeps the session's copy, and for X that is the current
+ * iterate (a warm start).  L has the form it had at creation (one value or V
+ * of them).  The scalars are always read: min and max (bounds kind only),
+ * rho, condMin, difRcd, difTol, itMax.  Everything that depends on the graph
+ * or on A alone is kept (orders, incidence, tile tables, the diagonal of A^tA,
+ * a sparse A's CSR view); the loop variant chosen at creation is kept too.
+ * The captured graphs are dropped and the chunk graph is instantiated again.
+ * The cost is a few streaming passes over the value arrays and the first
+ * preconditioning.
+ *
+ * PFDR_ERR_ARG, naming the offence and before any device work (the session
+ * then still holds its problem and can go on running): a session not created
+ * reusable; the simplex kind; a partitioned session; La_l1 or L given where
+ * the session was created without it (a NULL La_l1 keeps the session's, so
+ * the weights cannot be taken away either); min > max or a NaN bound; itMax
+ * above the creation's (the records are sized by it); difTol / difRcd that
+ * would switch the tracking of the iterate evolution (difTol > 0 || difRcd >
+ * 0 || record_dif) on or off, move difRcd between zero and non-zero, or in
+ * any other way change the loop variant chosen at creation. */
+typedef struct pfdr_reload {
+    int mem;              /* PFDR_MEM_*: location of every array below */
+    const void *X;        /* initial iterate (V); NULL: the current iterate */
+    const void *Y;        /* as pfdr_problem.Y; NULL: kept */
+    const void *La_d1;    /* length E; NULL: kept */
+    const void *La_l1;    /* length V (l1 kind); NULL: kept */
+    const void *L;        /* one value or V, as at creation; NULL: kept */
+    double min, max;      /* bounds kind */
+    double rho, condMin, difRcd, difTol;
+    int itMax;            /* <= the creation's */
+} pfdr_reload;
+int pfdr_session_create_reusable(pfdr_session **out, const pfdr_problem *p, const pfdr_csc *A);
+int pfdr_session_reload(pfdr_session *s, const pfdr_reload *r);
 
 /* ------------------------------------------- dense matrices (CP builder) -- */
 /* Gram matrix on the matrix cores (exact-f32 / f64 MFMA, fixed-order
