@@ -13,6 +13,12 @@
 //                         :636-648), per-vertex metric simplex projection,
 //                         evolution partials (l1 or label changes) and the
 //                         NEXT explicit step FP          ref :651-691, :567-587
+//                         one block of floor(256 / K) vertices per workgroup:
+//                         partitions, PFDR_SX_M=1 and, as its body
+//                         sx_vertex_block, the one-workgroup k_sx_tiny_iterate
+//     k_sx_vertex_tile  : (K <= 64, one GPU) the same for two such blocks per
+//                         workgroup, both blocks' loads in flight together;
+//                         the same sums and partials bit for bit
 //     k_sx_vertex_wide  : (K > 64) the same, one wave per vertex: coalesced
 //                         K-runs, sums in registers, the projection on the
 //                         whole wave (pfdr_proj.hpp); K > 1024 in memory
@@ -738,16 +744,12 @@ struct SxVArgs {
     // P lives in the .x half of PF only (no P store; the evolution reads
     // the old P from PF; SimplexSession::sync_p extracts it when asked)
     int nop;
-    // tile-ordered sessions (sx_tile_sum): per vertex block a 32-int record
-    // of its runs (null: no tiles; a block whose record says 0 runs takes
-    // the CSR gather) and the slot of every edge end in its block's list
-    const int *trec;
-    const unsigned short *sl;
-    int nparts;  // the fused sweep's blocks (the tile sweep's sub-blocks)
-    // the fused sweep's per-block incidence lists, padded to capb entries
-    // (idxp[blk * capb + j] = idx[ptr[v0] + j]; null: read idx through ptr):
-    // a block loads its list with addresses that depend on nothing loaded,
-    // beside its CSR pointers -- one round of loads fewer before the gathers
+    int nparts;  // k_sx_vertex_tile: the one-block sweep's blocks (its M sub-blocks' partials)
+    // the one-GPU sweep's per-workgroup incidence lists, padded to capb
+    // entries (idxp[blk * capb + j] = idx[ptr[v0] + j], v0 the workgroup's
+    // first vertex; null: read idx through ptr): a workgroup loads its list
+    // with addresses that depend on nothing loaded, beside its CSR pointers
+    // -- one round of loads fewer before the gathers
     const unsigned *idxp;
     int capb;
     // zoff: the padded lists hold Z element offsets (u end e: e K, v end e:
@@ -875,121 +877,7 @@ __device__ __forceinline__ real sx_item_sum(const SxVArgs<real> &a, long v, int 
     return sx_item_sum_from(a, v, k, a.idx, a.ptr[v], a.ptr[v + 1], sx_inv(a, v, v * a.c.K + k));
 }
 
-// ---------------------------------------- tile-ordered sums (K <= 64) ---
-// Ordered DR averages of vertex block blk from its tile runs (SxVArgs::trec,
-// see k_sx_tile_keys): the u-end rows of Z of the block's own edges (one
-// run) and the v-end rows of the (u block, blk) tiles (a few runs), read
-// once, coalesced, by this workgroup alone, and written into LDS at their
-// SLOT -- the (e, side) rank in the block's CSR-ordered list (sl) -- so
-// that each (vertex, label) lane then adds its vertex's entries in the
-// reference's order (ref :636-648) with the products of sx_item_sum: the
-// same sums bit for bit, one round of loads (record, then the runs) where
-// the CSR gather had two dependent ones (pointers, addresses, values).
-// Record: [runs n, u start, u count, (v start, count) x (n - 1)] in edge
-// units, n <= kSxRuns; the lane's slots [my0, my1) from the CSR pointers.
-constexpr int kSxRuns = 15, kSxRec = 32;
-template <typename real> struct SxTileCap { static constexpr int v = 2560; };  // LDS reals
-template <> struct SxTileCap<double> { static constexpr int v = 1280; };
-
-template <typename real, int M>
-struct SxTileLds {
-    static constexpr int items = M * kBlock;
-    static constexpr int cap = M * SxTileCap<real>::v;  // staged reals (K per list entry)
-};
-
-// Stage block blk's runs into LDS by slot: zl[slot * K + k] = Z, and with
-// WA the weights (per-edge La_d1: al[slot]; A1: al[slot * K + k]).  All
-// lanes of the workgroup take part (barriers).
-template <typename real, bool WA, int M>
-__device__ __forceinline__ void sx_tile_stage(const SxVArgs<real> &a, int blk, int t, real *zl,
-                                              real *al, int *rt) {
-    const int K = a.c.K;
-    const int lane = t & (kWave - 1);
-    const int rv = lane < kSxRec ? a.trec[(long)blk * kSxRec + lane] : 0;
-    const int nr = __builtin_amdgcn_readfirstlane(__shfl(rv, 0, kWave));
-    // run r in lane r: start, length (edge ends); values K per end (the
-    // shuffles run with the whole wave active: a lane reads another's
-    // register only while that lane is active)
-    const int st = __shfl(rv, min(1 + 2 * lane, kWave - 1), kWave);
-    const int lnr = __shfl(rv, min(2 + 2 * lane, kWave - 1), kWave);
-    int P = (lane < nr ? lnr : 0) * K;  // inclusive prefix of the runs' values
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int y = __shfl_up(P, o, kWave);
-        if (lane >= o) P += y;
-    }
-    const int tot = __builtin_amdgcn_readlane(P, kWave - 1);
-    // the run table in LDS for the item loop below (its lanes diverge)
-    if (t < kSxRuns + 1) {
-        rt[t] = t < nr ? st : 0;
-        rt[kSxRuns + 1 + t] = t < nr ? P : 0x7fffffff;
-    }
-    __syncthreads();
-    const long E = a.E;
-    const bool per_e = WA && !a.A1;  // per-edge La_d1: one weight per slot
-    const int *rst = rt, *rpr = rt + kSxRuns + 1;
-    // off / K as umulhi(off, ceil(2^32 / K)): exact for off < 2^20, K < 4096
-    const unsigned mK = (unsigned)((0x100000000ull + K - 1) / K);
-    // each lane walks values q = t, t + 256, ...: its run only advances;
-    // a block's list fits the LDS (k_sxt_rec), so all of its loads issue in
-    // ONE round (U values per lane in flight)
-    int r = 0, pend = rpr[0], pbeg = 0;
-    constexpr int U = SxTileLds<real, M>::cap / kBlock;
-    for (int q0 = t; q0 < tot; q0 += U * kBlock) {
-        real z[U], w[U];
-        int sl[U], kk[U];
-        bool ok[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int q = q0 + u * kBlock;
-            ok[u] = q < tot;
-            const int qq = ok[u] ? q : tot - 1;
-            while (pend <= qq) {
-                pbeg = pend;
-                pend = rpr[++r];
-            }
-            const int sr = rst[r];
-            const unsigned off = (unsigned)(qq - pbeg);
-            const unsigned ei = __umulhi(off, mK);
-            kk[u] = (int)(off - ei * (unsigned)K);
-            const long p = (long)sr + ei;
-            const bool sv = r > 0;
-            z[u] = (sv ? a.Zv : a.Zu)[p * K + kk[u]];
-            sl[u] = a.sl[(sv ? E : 0) + p];
-            w[u] = real(0);
-            if (WA) w[u] = a.A1 ? a.A1[p * K + kk[u]] : (kk[u] == 0 ? a.La_d1[p] : real(0));
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++)
-            if (ok[u]) {
-                zl[sl[u] * K + kk[u]] = z[u];
-                if (WA) {
-                    if (!per_e) al[sl[u] * K + kk[u]] = w[u];
-                    else if (kk[u] == 0) al[sl[u]] = w[u];
-                }
-            }
-    }
-    __syncthreads();
-}
-
-// the ordered sum of item (v, k) from the staged list: its vertex's slots
-// [ptr[v] - ptr[v0], ptr[v + 1] - ptr[v0]) in the reference's order, each
-// term (a * 1/Aux) * z as sx_item_sum forms it
-template <typename real>
-__device__ __forceinline__ real sx_tile_item(const SxVArgs<real> &a, int my0, int my1, int k,
-                                             real inv, const real *zl, const real *al, bool wa) {
-    const int K = a.c.K;
-    const bool per_e = !a.A1;
-    const real la0 = a.la0;
-    real s = real(0);
-    for (int j = my0; j < my1; j++) {
-        const real an = !wa ? la0 : (per_e ? al[j] : al[j * K + k]);
-        s += (an * inv) * zl[j * K + k];
-    }
-    return s;
-}
-
-// One block of the fused vertex sweep: NT lanes (t = the lane within
+// One block of the fused vertex sweep: kBlock lanes (t = the lane within
 // them) with their own xs / ms / red in LDS.  Every lane of the calling
 // workgroup reaches the same barriers (a block past the last, blk >= nb, has
 // no live lane); the block's evolution partial goes to *part_out (lane 0).
@@ -999,7 +887,7 @@ __device__ __forceinline__ real sx_tile_item(const SxVArgs<real> &a, int my0, in
 // lidx: the padded block list's LDS copy (SxVArgs::idxp); x0s: the raw
 // x[0] of each vertex (then the items divide by their metric in parallel and
 // the walk takes proj_simplex_column_div), null: the walk divides
-template <typename real, int NT, bool SPLIT = false>
+template <typename real, bool SPLIT = false>
 __device__ __forceinline__ void sx_vertex_block(const SxVArgs<real> &a, int blk, int t, real *xs,
                                                 real *ms, real *red, real *part_out,
                                                 unsigned *lidx = nullptr, real *x0s = nullptr) {
@@ -1028,7 +916,7 @@ __device__ __forceinline__ void sx_vertex_block(const SxVArgs<real> &a, int blk,
             inv = sx_inv(a, v, i);
         }
         const long lb = (long)blk * a.capb;
-        for (int q = t; q < a.capb; q += NT) lidx[q] = a.idxp[lb + q];
+        for (int q = t; q < a.capb; q += kBlock) lidx[q] = a.idxp[lb + q];
         j0 -= b0;
         j1 -= b0;
         __syncthreads();
@@ -1086,28 +974,25 @@ __device__ __forceinline__ void sx_vertex_block(const SxVArgs<real> &a, int blk,
     }
     if (a.track) {
         dif = wave_sum(dif);
-        if (NT > kWave) {
-            if ((t & (kWave - 1)) == 0) red[t / kWave] = dif;
-            __syncthreads();
-            if (t == 0) for (int q = 1; q < NT / kWave; q++) dif += red[q];
-        }
+        if ((t & (kWave - 1)) == 0) red[t / kWave] = dif;
+        __syncthreads();
+        if (t == 0) for (int q = 1; q < kBlock / kWave; q++) dif += red[q];
         if (t == 0 && blk < a.nb) *part_out = dif;
     }
 }
 
 constexpr int kSxPadPer = 8;  // entries of a padded block list per lane, at most
-constexpr int kSxNtDefault = 256;  // the fused sweep's workgroup width (fused_sweep_setup)
-constexpr int kSxMDefault = 2;     // its vertex blocks per workgroup (fused_sweep_setup)
-template <typename real, int NT, bool SPLIT = false>
-__global__ __launch_bounds__(NT) void k_sx_vertex_sweep(SxVArgs<real> a) {
+constexpr int kSxMDefault = 2;  // the one-GPU sweep's vertex blocks per workgroup (fused_sweep_setup)
+template <typename real, bool SPLIT = false>
+__global__ __launch_bounds__(kBlock) void k_sx_vertex_sweep(SxVArgs<real> a) {
     if (a.ctrl && a.ctrl->halt) return;
-    __shared__ real xs[NT], ms[NT];
-    __shared__ real red[NT / kWave];
-    __shared__ unsigned lidx[kSxPadPer * NT];
-    __shared__ real x0s[NT];
+    __shared__ real xs[kBlock], ms[kBlock];
+    __shared__ real red[kBlock / kWave];
+    __shared__ unsigned lidx[kSxPadPer * kBlock];
+    __shared__ real x0s[kBlock];
     const int blk = xcd_block(blockIdx.x, a.nb, a.xcd);
     if (blk >= a.nb) return;
-    sx_vertex_block<real, NT, SPLIT>(a, blk, threadIdx.x, xs, ms, red, a.part + blk, lidx, x0s);
+    sx_vertex_block<real, SPLIT>(a, blk, threadIdx.x, xs, ms, red, a.part + blk, lidx, x0s);
 }
 
 // the padded lists (SxVArgs::idxp) and their width: the largest block's
@@ -1137,26 +1022,20 @@ __global__ void k_sx_pad_idx(long n, int capb, int vb, int V, const int *__restr
     idxp[q] = x;
 }
 
-// Tile-ordered sessions: one workgroup per tile block of M * vb vertices (M
-// items per lane), its sums from the block's tile runs (sx_tile_sum) or,
-// for a block without a record, the CSR gather.  M > 1 gives each
+// The one-GPU sweep (M = 2): one workgroup per M consecutive vertex blocks
+// (M * vb vertices, M items per lane), the CSR gather from the workgroup's
+// padded list in LDS (SxVArgs::idxp over its M * vb vertices) when there is
+// one, the M items' gathers in flight together.  M > 1 gives each
 // workgroup's load rounds and projection walk M times the work: the sweep
 // is bound by the latency of those serial phases, not by its bytes.
-
-// ST: staged tile sums (the block's record); else the CSR gather, from the
-// block's padded list in LDS (SxVArgs::idxp over M * vb vertices) when there
-// is one -- M items per lane, their gathers in flight together
-template <typename real, bool SPLIT, bool WA, int M, bool ST = true>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ST || M > 2 || sizeof(real) > 4 ? 1 : 8)))
+template <typename real, bool SPLIT, int M>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(real) > 4 ? 1 : 8)))
 void k_sx_vertex_tile(SxVArgs<real> a) {
     if (a.ctrl && a.ctrl->halt) return;
-    using L = SxTileLds<real, M>;
-    __shared__ real xs[L::items], ms[L::items], x0s[L::items];
+    constexpr int items = M * kBlock;
+    __shared__ real xs[items], ms[items], x0s[items];
     __shared__ real red[M][kBlock / kWave];
-    __shared__ real zl[ST ? L::cap : 1];
-    __shared__ real al[ST && WA ? L::cap : 1];
-    __shared__ int rt[2 * (kSxRuns + 1)];
-    __shared__ unsigned lidx[ST ? 1 : kSxPadPer * kBlock];
+    __shared__ unsigned lidx[kSxPadPer * kBlock];
     const int blk = xcd_block(blockIdx.x, a.nb, a.xcd);
     if (blk >= a.nb) return;
     const int t = threadIdx.x;
@@ -1190,12 +1069,7 @@ void k_sx_vertex_tile(SxVArgs<real> a) {
             j1[u] = a.ptr[vi[u] + 1];
         }
     }
-    if (ST && a.trec[(long)blk * kSxRec] > 0) {  // block-uniform
-        sx_tile_stage<real, WA, M>(a, blk, t, zl, al, rt);
-#pragma unroll
-        for (int u = 0; u < M; u++)
-            if (live[u]) x[u] = sx_tile_item(a, j0[u] - b0, j1[u] - b0, kk[u], inv[u], zl, al, WA);
-    } else if (!ST && a.idxp) {  // the padded list (SxVArgs::idxp) into LDS
+    if (a.idxp) {  // the padded list (SxVArgs::idxp) into LDS
         const long lb = (long)blk * a.capb;
         for (int q = t; q < a.capb; q += kBlock) lidx[q] = a.idxp[lb + q];
         __syncthreads();
@@ -1823,8 +1697,8 @@ __global__ __launch_bounds__(kSxTiny) void k_sx_tiny_iterate(SxTinyArgs<real> t)
         __syncthreads();
         for (int b0 = 0; b0 < a.nb; b0 += NB) {
             const int blk = b0 + sub;
-            sx_vertex_block<real, kBlock>(a, blk, lt, xs + sub * kBlock, ms + sub * kBlock,
-                                                 red + sub * (kBlock / kWave), bpart + blk);
+            sx_vertex_block<real>(a, blk, lt, xs + sub * kBlock, ms + sub * kBlock,
+                                  red + sub * (kBlock / kWave), bpart + blk);
             __syncthreads();  // xs / ms / red reused by the next four blocks
         }
         if (t.ctrl) {  // k_sx_finalize on the first 256 lanes: its loop and block_sum's tree
@@ -2074,77 +1948,6 @@ __global__ void k_sx_permute(long E, const unsigned *__restrict__ perm, const re
     if (p < E) dst[p] = src[perm[p]];
 }
 
-// sl[address] = the slot of the edge end at that address (e: u end, E + e:
-// v end) in its vertex block's CSR list (vb vertices per block; clamped:
-// a block past 65,535 entries has no record)
-__global__ void k_sxt_slots(int V, int vb, const int *__restrict__ ptr,
-                            const unsigned *__restrict__ idx, unsigned short *__restrict__ sl) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= V) return;
-    const int base = ptr[v - v % vb];
-    for (int j = ptr[v]; j < ptr[v + 1]; j++) {
-        const int d = j - base;
-        sl[idx[j]] = (unsigned short)(d < 65535 ? d : 65535);
-    }
-}
-
-// ustart[b] = first position whose u end lies in block >= b (edges sorted
-// by u block), ustart[nb] = E
-__global__ void k_sxt_ustart(long E, int nb, int vb, const int *__restrict__ Eu,
-                             int *__restrict__ ustart) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > E) return;
-    const int lo = p == 0 ? 0 : Eu[p - 1] / vb + 1;
-    const int hi = p == E ? nb : Eu[p] / vb;
-    for (int b = lo; b <= hi; b++) ustart[b] = (int)p;
-}
-
-// v-end runs: maximal stretches of positions whose v end lies in one block
-__global__ void k_sxt_runs_count(long E, int vb, const int *__restrict__ Ev, int *__restrict__ cnt) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= E) return;
-    const int b = Ev[i] / vb;
-    if (i == 0 || Ev[i - 1] / vb != b) atomicAdd(cnt + b, 1);
-}
-__global__ void k_sxt_runs_fill(long E, int vb, const int *__restrict__ Ev,
-                                const int *__restrict__ tptr, int *__restrict__ fill,
-                                int *__restrict__ tstart, int *__restrict__ tlen) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= E) return;
-    const int b = Ev[i] / vb;
-    if (i != 0 && Ev[i - 1] / vb == b) return;
-    long q = i + 1;
-    while (q < E && Ev[q] / vb == b) q++;
-    const int j = tptr[b] + atomicAdd(fill + b, 1);
-    tstart[j] = (int)i;
-    tlen[j] = (int)(q - i);
-}
-
-// block b's record (sx_tile_sum): [runs, u start, u count, (v start, v
-// count) x runs - 1]; 0 runs (the CSR gather) when it has more than kSxRuns
-// runs or its list exceeds the LDS (cap reals, K per entry)
-__global__ void k_sxt_rec(int nb, int V, int vb, int K, int cap, const int *__restrict__ ptr,
-                          const int *__restrict__ ustart, const int *__restrict__ tptr,
-                          const int *__restrict__ tstart, const int *__restrict__ tlen,
-                          int *__restrict__ rec, int *__restrict__ nok) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    int *r = rec + (long)b * kSxRec;
-    for (int q = 0; q < kSxRec; q++) r[q] = 0;
-    const long v0 = (long)b * vb, v1 = min(v0 + vb, (long)V);
-    const long n = (long)ptr[v1] - ptr[v0];
-    const int t0 = tptr[b], nt = tptr[b + 1] - t0;
-    if (nt + 1 > kSxRuns || n * K > cap) return;
-    r[0] = nt + 1;
-    r[1] = ustart[b];
-    r[2] = ustart[b + 1] - ustart[b];
-    for (int q = 0; q < nt; q++) {
-        r[3 + 2 * q] = tstart[t0 + q];
-        r[4 + 2 * q] = tlen[t0 + q];
-    }
-    atomicAdd(nok, 1);
-}
-
 // *bad += the entries of La_d1 that differ from La_d1[0].  (The session's
 // own kernel: the quadratic file's uniformity kernel, launched from here, made
 // the runtime load that file's code object, which cost C4 1 %)
@@ -2207,7 +2010,7 @@ class SimplexSession final : public IterLoop<real> {
   private:
     using L = IterLoop<real>;
     using L::stream, L::prof, L::device, L::device_bytes, L::ghosts, L::tiled_blocks, L::tiny;
-    using L::record_blocks, L::la_uniform, L::seqdif;
+    using L::la_uniform, L::seqdif;
     using L::halo_, L::ctrl_, L::hctrl_, L::itMax_, L::verbose_, L::it_, L::stopped_, L::chunk_;
     using L::tiny_, L::graphs_ok_, L::capturable_, L::kSpecMax, L::spec_, L::sd_, L::seqdif_;
     using L::chain_, L::route_, L::dws_, L::red_, L::push_ctrl, L::drop_graphs;
@@ -2259,7 +2062,13 @@ class SimplexSession final : public IterLoop<real> {
     Incidence inc_;
     HostPins pins_;  // caller arrays pinned for the setup copies
     int nbv_, nbe_;
-    int vb_ = 0, nbs_ = 0;  // fused vertex sweep (K <= 64): vertices per block, blocks
+    // fused vertex sweep (K <= 64): vertices per block, blocks (the number of
+    // its evolution partials, whatever the workgroups)
+    int vb_ = 0, nbs_ = 0;
+    // its workgroups: sxm_ blocks each (2: k_sx_vertex_tile on one GPU,
+    // fused_sweep_setup; 1: k_sx_vertex_sweep, every partition's and
+    // PFDR_SX_M=1), wgv_ = sxm_ vb_ vertices, nwg_ of them
+    int sxm_ = 1, wgv_ = 0, nwg_ = 0;
     int nbw_ = 0;           // wide vertex sweep (K > 64): blocks
     int gnv_ = 0;           // its vertices per group (0: a wave per vertex, in memory)
     DevBuf<unsigned char> act_;  // its active sets when K > 1024
@@ -2267,20 +2076,10 @@ class SimplexSession final : public IterLoop<real> {
     // kSxTileMinVK (edge, label) entries)
     bool sxtile_ = false;
     static constexpr long kSxTileMinVK = 1L << 21;
-    int sxtm_ = 2, tbv_ = 0, nbt_ = 0;  // items per lane, tile block vertices, tile blocks
-    DevBuf<int> trec_;              // per tile block: its runs (k_sxt_rec)
-    DevBuf<unsigned short> sl_;     // slot of every edge end (k_sxt_slots)
-    DevBuf<unsigned> idxp_;         // padded block lists (SxVArgs::idxp), capb_ wide
+    DevBuf<unsigned> idxp_;         // padded workgroup lists (SxVArgs::idxp), capb_ wide
     int capb_ = 0;
-    // the one-GPU fused sweep's workgroups: snt_ lanes, svb_ vertices,
-    // snb_ blocks (PFDR_SX_NT = 64, 128, 256; fused_sweep_setup)
-    int snt_ = kBlock, svb_ = 0, snb_ = 0;
     bool zoff_ = false;  // the padded lists hold Z offsets (SxVArgs::zoff)
-    // the one-GPU fused sweep on workgroups of M vertex blocks (M items per
-    // lane, k_sx_vertex_tile without staging; PFDR_SX_M = 1, 2, 4): sxm_ > 1
-    int sxm_ = 1;
     void fused_sweep_setup();
-    void build_sx_tiles();
     // one La_d1 for every edge (k_sx_uniform_check at setup): a kernel argument
     bool la_u_ = false;
     real la0_ = real(0);
@@ -2327,31 +2126,16 @@ class SimplexSession final : public IterLoop<real> {
         if (halo_) halo_->pull(PF_.p, K_ * (int)sizeof(SxR2<real>), stream);
     }
     void push_wz();
-    template <bool SPLIT>
-    void launch_m_s(const SxVArgs<real> &a) {
+    // the fused vertex sweep (K <= 64) on the session's workgroups (sxm_)
+    void launch_fused(const SxVArgs<real> &a, bool split) {
         const int g = xcd_grid(a.nb, a.xcd);
-        if (sxm_ == 2) k_sx_vertex_tile<real, SPLIT, false, 2, false><<<g, kBlock, 0, stream>>>(a);
-        else k_sx_vertex_tile<real, SPLIT, false, 4, false><<<g, kBlock, 0, stream>>>(a);
-    }
-    void launch_m(const SxVArgs<real> &a, bool split) {
-        split ? launch_m_s<true>(a) : launch_m_s<false>(a);
-    }
-    template <bool SPLIT>
-    void launch_fused(const SxVArgs<real> &a, int g) {
-        if (snt_ == 64) k_sx_vertex_sweep<real, 64, SPLIT><<<g, 64, 0, stream>>>(a);
-        else if (snt_ == 128) k_sx_vertex_sweep<real, 128, SPLIT><<<g, 128, 0, stream>>>(a);
-        else k_sx_vertex_sweep<real, kBlock, SPLIT><<<g, kBlock, 0, stream>>>(a);
-    }
-    template <bool SPLIT, bool WA>
-    void launch_tile_m(const SxVArgs<real> &a) {
-        const int g = xcd_grid(a.nb, a.xcd);
-        if (sxtm_ == 1) k_sx_vertex_tile<real, SPLIT, WA, 1><<<g, kBlock, 0, stream>>>(a);
-        else if (sxtm_ == 2) k_sx_vertex_tile<real, SPLIT, WA, 2><<<g, kBlock, 0, stream>>>(a);
-        else k_sx_vertex_tile<real, SPLIT, WA, 4><<<g, kBlock, 0, stream>>>(a);
-    }
-    void launch_tile(const SxVArgs<real> &a, bool split, bool wa) {
-        if (split) wa ? launch_tile_m<true, true>(a) : launch_tile_m<true, false>(a);
-        else wa ? launch_tile_m<false, true>(a) : launch_tile_m<false, false>(a);
+        if (sxm_ == 2) {
+            if (split) k_sx_vertex_tile<real, true, 2><<<g, kBlock, 0, stream>>>(a);
+            else k_sx_vertex_tile<real, false, 2><<<g, kBlock, 0, stream>>>(a);
+        } else {
+            if (split) k_sx_vertex_sweep<real, true><<<g, kBlock, 0, stream>>>(a);
+            else k_sx_vertex_sweep<real, false><<<g, kBlock, 0, stream>>>(a);
+        }
     }
     template <bool SPLIT>
     void launch_wide(SxVArgs<real> a) {
@@ -2427,29 +2211,22 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
         }
     }
     check_endpoints(Eu_.p, Ev_.p, E_, Vg_, s);
+    if (K_ <= 64) {  // the fused sweep's blocks (fused_sweep_setup: its workgroups)
+        vb_ = wgv_ = kBlock / K_;
+        nbs_ = nwg_ = (int)((V_ + vb_ - 1) / vb_);
+    }
     DevBuf<unsigned> perm;  // tile order: position -> original edge id
     {
         const char *t = getenv("PFDR_SX_TILE");
         const int want = t ? atoi(t) : -1;
-        // tile blocks of M vertex blocks (the staged sweep k_sx_vertex_tile,
-        // PFDR_SX_STAGE=1; PFDR_SX_TILEM = 1, 2, 4; the CSR gather's blocks
-        // are the M = 1 ones)
-        const char *tm = getenv("PFDR_SX_TILEM");
-        const char *stg = getenv("PFDR_SX_STAGE");
-        sxtm_ = tm ? atoi(tm) : (stg && stg[0] == '1') ? 2 : 1;
-        if (sxtm_ != 1 && sxtm_ != 2 && sxtm_ != 4) throw std::runtime_error("PFDR_SX_TILEM: 1, 2 or 4");
-        const int vb = K_ <= 64 ? sxtm_ * (kBlock / K_) : 0;
-        const long nb = vb ? ((long)V_ + vb - 1) / vb : 0;
-        tbv_ = vb;
-        nbt_ = (int)nb;
-        sxtile_ = !halo_ && vb && E_ > 1 && want != 0 && (want > 0 || VK_ >= kSxTileMinVK);
-        if (sxtile_) {
+        sxtile_ = !halo_ && vb_ && E_ > 1 && want != 0 && (want > 0 || VK_ >= kSxTileMinVK);
+        if (sxtile_) {  // tiles of the one-block sweep's blocks
             int vbits = 1;
-            while (vbits < 31 && (1L << vbits) < nb) vbits++;
+            while (vbits < 31 && (1L << vbits) < nbs_) vbits++;
             DevBuf<unsigned long long> k(E_), ks(E_);
             DevBuf<unsigned> v(E_);
             perm.alloc(E_);
-            k_sx_tile_keys<<<grid_for(E_), kBlock, 0, s>>>(E_, vb, vbits, Eu_.p, Ev_.p, k.p, v.p);
+            k_sx_tile_keys<<<grid_for(E_), kBlock, 0, s>>>(E_, vb_, vbits, Eu_.p, Ev_.p, k.p, v.p);
             PFDR_HIP(hipGetLastError());
             radix_sort_pairs_stable<unsigned long long>(k.p, ks.p, v.p, perm.p, E_, 2 * vbits, s);
             DevBuf<int> nu(E_), nv(E_);
@@ -2459,7 +2236,7 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
             std::swap(Ev_.p, nv.p);
             PFDR_HIP(hipStreamSynchronize(s));
         }
-        tiled_blocks = sxtile_ ? nb : 0;  // tile blocks (every one's edges in tile order)
+        tiled_blocks = sxtile_ ? nbs_ : 0;  // tile blocks (every one's edges in tile order)
     }
     contribution_incidence(Eu_.p, Ev_.p, E_, V_, sxtile_ ? perm.p : eg.p, e_offset, halo_.get(),
                            inc_, s);
@@ -2491,18 +2268,7 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
         else PFDR_HIP(hipMemcpyAsync(q.first->p, q.second, VK_ * sizeof(real), kind, s));
         pullK(*q.first);
     }
-    if (K_ <= 64) {
-        vb_ = kBlock / K_;
-        nbs_ = (int)((V_ + vb_ - 1) / vb_);
-        svb_ = vb_;  // (fused_sweep_setup may narrow the one-GPU sweep's blocks)
-        snb_ = nbs_;
-        // the staged tile sweep (k_sx_vertex_tile) is opt-in: PFDR_SX_STAGE=1.
-        // On C4 it measured slower than the CSR gather over the same
-        // tile-ordered edges (1.10 vs 0.69 ms: its staging costs more issue
-        // and LDS work than the gather's one extra load round)
-        const char *st = getenv("PFDR_SX_STAGE");
-        if (sxtile_ && st && st[0] == '1') build_sx_tiles();
-    } else {  // groups of vertices with their columns in LDS, or a wave per vertex
+    if (!vb_) {  // K > 64: groups of vertices with their columns in LDS, or a wave per vertex
         gnv_ = SxGroup<real>::nv_for(K_, SxGroup<real>::kNV);
         const long per = gnv_ ? gnv_ : (long)kSxWideVpw * (kBlock / kWave);
         nbw_ = (int)((V_ + per - 1) / per);
@@ -2526,7 +2292,7 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
     wz_.alloc(2 * EKn + (size_t)R_ * K_);  // [side][e][k], then the received tail
     nbv_ = grid_for(V_);
     nbe_ = grid_for(E_);
-    part_.alloc(std::max(std::max(nbv_, nbs_), nbw_));  // (nbt_ <= nbs_)
+    part_.alloc(std::max(std::max(nbv_, nbs_), nbw_));
     if (rec_obj_) { opart_.alloc((size_t)nbv_ + nbe_ + 1); Obj_.alloc((size_t)itMax_ + 1); }
     if (rec_dif_) Dif_.alloc(itMax_ > 0 ? itMax_ : 1);
     if (track_ == 2) {
@@ -2611,38 +2377,6 @@ SimplexSession<real>::SimplexSession(const pfdr_problem *p) {
                               sizeof(SxR2<real>));
 }
 
-// the runs and slots of every vertex block of a tile-ordered session (see
-// sx_tile_sum); blocks whose runs or list do not fit keep the CSR gather
-template <typename real>
-void SimplexSession<real>::build_sx_tiles() {
-    hipStream_t s = stream;
-    const int nb = nbt_, vb = tbv_;
-    sl_.alloc((size_t)2 * E_);
-    k_sxt_slots<<<grid_for(V_), kBlock, 0, s>>>(V_, vb, inc_.ptr.p, inc_.idx.p, sl_.p);
-    DevBuf<int> ustart((size_t)nb + 1), cnt(nb), fill(nb), nok(1);
-    k_sxt_ustart<<<grid_for(E_ + 1), kBlock, 0, s>>>(E_, nb, vb, Eu_.p, ustart.p);
-    PFDR_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * nb, s));
-    PFDR_HIP(hipMemsetAsync(fill.p, 0, sizeof(int) * nb, s));
-    PFDR_HIP(hipMemsetAsync(nok.p, 0, sizeof(int), s));
-    k_sxt_runs_count<<<grid_for(E_), kBlock, 0, s>>>(E_, vb, Ev_.p, cnt.p);
-    PFDR_HIP(hipGetLastError());
-    std::vector<int> h(nb), tp((size_t)nb + 1, 0);
-    PFDR_HIP(hipMemcpyAsync(h.data(), cnt.p, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < nb; b++) tp[b + 1] = tp[b] + h[b];
-    DevBuf<int> tptr((size_t)nb + 1), tstart(tp[nb] ? tp[nb] : 1), tlen(tp[nb] ? tp[nb] : 1);
-    PFDR_HIP(hipMemcpyAsync(tptr.p, tp.data(), sizeof(int) * (nb + 1), hipMemcpyHostToDevice, s));
-    k_sxt_runs_fill<<<grid_for(E_), kBlock, 0, s>>>(E_, vb, Ev_.p, tptr.p, fill.p, tstart.p, tlen.p);
-    trec_.alloc((size_t)nb * kSxRec);
-    k_sxt_rec<<<grid_for(nb), kBlock, 0, s>>>(nb, V_, vb, K_, sxtm_ * SxTileCap<real>::v, inc_.ptr.p,
-                                              ustart.p, tptr.p, tstart.p, tlen.p, trec_.p, nok.p);
-    PFDR_HIP(hipGetLastError());
-    int n = 0;
-    PFDR_HIP(hipMemcpyAsync(&n, nok.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    record_blocks = n;  // (tiled_blocks: every block's edges are in tile order)
-}
-
 // ref :64-370
 template <typename real>
 void SimplexSession<real>::precondition(bool init) {
@@ -2697,56 +2431,38 @@ void SimplexSession<real>::objective() {
 }
 
 // The one-GPU fused sweep (K <= 64, not the one-workgroup path): its
-// workgroup width and the padded block lists.  Narrower workgroups put more
-// of them on a CU: the sweep's time is the latency of each block's chain
-// (list and pointers, gathers, projection walk, stores), hidden by the other
-// blocks in flight.  Its evolution partials are per workgroup, so a tracked
-// solve with the tree statistic keeps the 256-lane blocks (its Dif rounds as
-// before); the sequential statistic and untracked solves take PFDR_SX_NT.
+// workgroups of M vertex blocks (PFDR_SX_M = 1 or 2, default 2) and their
+// padded lists.  The sweep's time is the latency of each workgroup's chain
+// (list and pointers, gathers, projection walk, stores): two blocks per
+// workgroup keep both blocks' loads in flight together.  The evolution
+// partials stay the one-block sweep's (nbs_ of them), so Dif rounds alike.
 template <typename real>
 void SimplexSession<real>::fused_sweep_setup() {
     hipStream_t s = stream;
-    snt_ = kBlock;
-    svb_ = vb_;
-    snb_ = nbs_;
-    const char *ntv = getenv("PFDR_SX_NT");
-    const int nt = ntv ? atoi(ntv) : kSxNtDefault;
-    if (nt != 64 && nt != 128 && nt != 256) throw std::runtime_error("PFDR_SX_NT: 64, 128 or 256");
     const char *mv = getenv("PFDR_SX_M");
     sxm_ = mv ? atoi(mv) : kSxMDefault;
-    if (sxm_ != 1 && sxm_ != 2 && sxm_ != 4) throw std::runtime_error("PFDR_SX_M: 1, 2 or 4");
-    if (trec_.p) sxm_ = 1;  // (the staged sweep has its own blocks)
-    if (sxm_ > 1) {  // workgroups of sxm_ vertex blocks (their partials: the 256-lane sweep's)
-        tbv_ = sxm_ * vb_;
-        nbt_ = (int)((V_ + tbv_ - 1) / tbv_);
-        svb_ = tbv_;  // (the padded lists below cover a workgroup's vertices)
-        snb_ = nbt_;
-    } else if ((!track_ || seqdif_) && !trec_.p && K_ <= nt) {
-        snt_ = nt;
-        svb_ = nt / K_;
-        snb_ = (int)((V_ + svb_ - 1) / svb_);
-        if ((size_t)snb_ > part_.n) part_.alloc((size_t)snb_);
-    }
-    // padded block lists (PFDR_SX_PAD=0 off): when the widest block's list
-    // fits the sweep's LDS list and the padding costs at most half the lists'
-    // size (regular graphs)
+    if (sxm_ != 1 && sxm_ != 2) throw std::runtime_error("PFDR_SX_M: 1 or 2");
+    wgv_ = sxm_ * vb_;
+    nwg_ = (int)((V_ + wgv_ - 1) / wgv_);
+    // padded workgroup lists (PFDR_SX_PAD=0 off): when the widest
+    // workgroup's list fits the sweep's LDS list and the padding costs at
+    // most half the lists' size (regular graphs)
     const char *pd = getenv("PFDR_SX_PAD");
     if (E_ > 0 && !(pd && pd[0] == '0')) {
         DevBuf<int> cb(1);
         PFDR_HIP(hipMemsetAsync(cb.p, 0, sizeof(int), s));
-        k_sx_block_max<<<grid_for(snb_), kBlock, 0, s>>>(snb_, svb_, V_, inc_.ptr.p, cb.p);
+        k_sx_block_max<<<grid_for(nwg_), kBlock, 0, s>>>(nwg_, wgv_, V_, inc_.ptr.p, cb.p);
         PFDR_HIP(hipGetLastError());
         int h = 0;
         PFDR_HIP(hipMemcpyAsync(&h, cb.p, sizeof(int), hipMemcpyDeviceToHost, s));
         PFDR_HIP(hipStreamSynchronize(s));
-        const long n = (long)snb_ * h;
-        if (h > 0 && h <= kSxPadPer * snt_ && n <= 3 * E_) {  // (2E list entries, at most 1.5 x)
-            // (sxm_ > 1: lists of kSxPadPer * 256 entries at most, as snt_ = 256)
+        const long n = (long)nwg_ * h;
+        if (h > 0 && h <= kSxPadPer * kBlock && n <= 3 * E_) {  // (2E list entries, at most 1.5 x)
             capb_ = h;
             idxp_.alloc((size_t)n);
             // (one GPU: no received entries; one edge weight until A1 exists)
             zoff_ = la_u_ && 2 * EK_ + K_ <= 0xffffffffL;
-            k_sx_pad_idx<<<grid_for(n), kBlock, 0, s>>>(n, h, svb_, V_, inc_.ptr.p, inc_.idx.p,
+            k_sx_pad_idx<<<grid_for(n), kBlock, 0, s>>>(n, h, wgv_, V_, inc_.ptr.p, inc_.idx.p,
                                                         idxp_.p, E_, zoff_ ? K_ : 0);
             PFDR_HIP(hipGetLastError());
         }
@@ -2785,8 +2501,7 @@ void SimplexSession<real>::body(int, int) {
     const bool gated = track_ || rec_obj_;
     const Ctrl<real> *c = gated ? ctrl_.p : nullptr;
     sweeps(c, 0);
-    // (the staged tile sweep writes the 256-lane fused sweep's partials)
-    const int nparts = (trec_.p || sxm_ > 1) ? nbs_ : vb_ ? snb_ : nbw_;
+    const int nparts = vb_ ? nbs_ : nbw_;
     if (seqdif_) {
         // the reference's sequential sum (ref :655-689), then its decision
         ProfScope ps(prof, "seq_evolution", s);
@@ -2856,28 +2571,9 @@ void SimplexSession<real>::sweeps(const Ctrl<real> *c, int t) {
     a.zfast = (!halo_ && la_u_ && 2 * EK_ + K_ <= 0xffffffffL) ? 1 : 0;
     if (vb_) {
         ProfScope ps(prof, "sx_vertex_sweep", s);
-        a.vb = svb_;
-        a.nb = snb_; a.xcd = xcd_fit(snb_, sx_xcd_v_);
-        const int g = xcd_grid(snb_, a.xcd);
-        if (trec_.p) {  // tile runs staged by slot (sx_tile_stage)
-            a.trec = trec_.p;
-            a.sl = sl_.p;
-            a.nparts = nbs_;  // (a.vb: the 256-lane sweep's; the tile blocks are M of them)
-            a.vb = vb_;
-            a.nb = nbt_;
-            a.xcd = xcd_fit(nbt_, sx_xcd_v_);
-            launch_tile(a, Po != nullptr, A1_.p || !la_u_);  // (weights staged with the runs)
-        } else if (sxm_ > 1) {  // workgroups of sxm_ vertex blocks, the CSR gather
-            a.nparts = nbs_;
-            a.vb = vb_;
-            a.nb = nbt_;
-            a.xcd = xcd_fit(nbt_, sx_xcd_v_);
-            launch_m(a, Po != nullptr);
-        } else if (Po) {
-            launch_fused<true>(a, g);
-        } else {
-            launch_fused<false>(a, g);
-        }
+        a.nparts = nbs_;
+        a.nb = nwg_; a.xcd = xcd_fit(nwg_, sx_xcd_v_);
+        launch_fused(a, Po != nullptr);
     } else {
         ProfScope ps(prof, "sx_vertex_wide", s);
         a.nb = nbw_; a.xs = Pavg_.p; a.act = act_.p;

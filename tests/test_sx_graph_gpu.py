@@ -43,8 +43,7 @@ def test_sx_graph_golden_identical(gpu_lib, name, fixed):
     c, g = G.load(name)
     res = []
     for env in ({}, {"PFDR_SX_TINY": "0"}, {"PFDR_SX_TINY": "100000000"},
-                {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1"},  # edges in tile order
-                {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1", "PFDR_SX_STAGE": "1"}):  # staged sweep
+                {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1"}):  # edges in tile order
         with _env(**env):
             res.append(G.replay(gpu_lib, c, fixed, obj=False, dif=True))
     X0, it0, _, D0 = res[0]
@@ -81,10 +80,7 @@ def test_sx_graph_sessions_identical(gpu_lib, case):
     for env in ({"PFDR_SX_TINY": "0"}, {"PFDR_SX_TINY": "0", "launch": "direct"},
                 {"PFDR_SX_TINY": "100000000"}, {},
                 {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1"},
-                {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1", "launch": "direct"},
-                {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1", "PFDR_SX_STAGE": "1"},
-                {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1", "PFDR_SX_STAGE": "1",
-                 "PFDR_SX_TILEM": "1"}):
+                {"PFDR_SX_TINY": "0", "PFDR_SX_TILE": "1", "launch": "direct"}):
         direct = env.pop("launch", None) == "direct"
         with _env(**env):
             s = pfdr.Session(pfdr.PFDR_KIND_SIMPLEX, dt, V, Eu.size, Eu, Ev,
@@ -141,8 +137,8 @@ def test_sx_tile_order_identical(gpu_lib, dt, K, al, difRcd):
     Q[: V // 3, 1 % K] += 1.5
     Q = (Q / Q.sum(axis=1, keepdims=True)).reshape(-1).astype(dt)
     res = []
-    for tile, stage in (("0", "0"), ("1", "0"), ("1", "1")):
-        with _env(PFDR_SX_TINY="0", PFDR_SX_TILE=tile, PFDR_SX_STAGE=stage):
+    for tile in ("0", "1"):
+        with _env(PFDR_SX_TINY="0", PFDR_SX_TILE=tile):
             s = pfdr.Session(pfdr.PFDR_KIND_SIMPLEX, dt, V, Eu.size, Eu, Ev, La, Q.copy(), Q,
                              K=K, al=al, rho=1.0, condMin=0.1, difRcd=difRcd, difTol=1e-6,
                              itMax=150, record_dif=True)
@@ -163,9 +159,9 @@ def test_sx_tile_order_identical(gpu_lib, dt, K, al, difRcd):
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
 @pytest.mark.parametrize("K,al", [(10, 0.1), (3, 0.0), (64, 1.0), (7, 0.1)])
 def test_sx_fused_widths_identical(gpu_lib, dt, K, al):
-    """The one-GPU fused sweep on workgroups of 64, 128 or 256 lanes
-    (PFDR_SX_NT) or of 2 / 4 vertex blocks (PFDR_SX_M), with and without the
-    padded block lists (PFDR_SX_PAD=0):
+    """The one-GPU fused sweep on workgroups of one or two vertex blocks
+    (PFDR_SX_M = 1: the one-block kernel of the partitions; 2: the default),
+    with and without the padded lists (PFDR_SX_PAD=0):
     identical iterates, counts and (sequential) Dif, tracked to a tolerance
     with reconditionings and at a fixed iteration count"""
     from cp_pfdr_graph_d1_amd import pfdr
@@ -180,11 +176,8 @@ def test_sx_fused_widths_identical(gpu_lib, dt, K, al):
     for kw in (dict(difTol=1e-6, difRcd=1e-2, evolution=pfdr.EVOLUTION_SEQUENTIAL),
                dict(difTol=0.0, difRcd=0.0)):
         res = []
-        for env in ({"PFDR_SX_M": "1"}, {"PFDR_SX_M": "2"}, {"PFDR_SX_M": "4"},
-                    {"PFDR_SX_M": "2", "PFDR_SX_PAD": "0"}, {"PFDR_SX_M": "1", "PFDR_SX_NT": "128"},
-                    {"PFDR_SX_M": "1", "PFDR_SX_NT": "64"},
-                    {"PFDR_SX_M": "1", "PFDR_SX_NT": "64", "PFDR_SX_PAD": "0"},
-                    {"PFDR_SX_M": "1", "PFDR_SX_PAD": "0"}):
+        for env in ({"PFDR_SX_M": "1"}, {"PFDR_SX_M": "2"},
+                    {"PFDR_SX_M": "2", "PFDR_SX_PAD": "0"}, {"PFDR_SX_M": "1", "PFDR_SX_PAD": "0"}):
             with _env(PFDR_SX_TINY="0", **env):
                 s = pfdr.Session(pfdr.PFDR_KIND_SIMPLEX, dt, V, Eu.size, Eu, Ev, La, Q.copy(), Q,
                                  K=K, al=al, rho=1.0, condMin=0.1, itMax=120, record_dif=True, **kw)
@@ -199,3 +192,19 @@ def test_sx_fused_widths_identical(gpu_lib, dt, K, al):
             assert it1 == it0
             assert np.array_equal(X1, X0)
             assert np.array_equal(D1[:it1], D0[:it0])
+
+
+def test_sx_m_out_of_range_refused(gpu_lib):
+    """PFDR_SX_M takes 1 or 2: four vertex blocks per workgroup measured
+    slower and its kernel is gone, so the session refuses the value, naming
+    the variable, rather than run another width unasked."""
+    from cp_pfdr_graph_d1_amd import pfdr
+    from cp_pfdr_graph_d1_amd.graphs import grid_graph
+    K, V = 3, 8 * 8
+    Eu, Ev = grid_graph((8, 8), 8)
+    Q = np.full(V * K, 1.0 / K, np.float32)
+    with _env(PFDR_SX_TINY="0", PFDR_SX_M="4"):
+        with pytest.raises(pfdr.PFDRError, match="PFDR_SX_M"):
+            pfdr.Session(pfdr.PFDR_KIND_SIMPLEX, np.float32, V, Eu.size, Eu, Ev,
+                         np.full(Eu.size, 0.05, np.float32), Q.copy(), Q, K=K, al=0.1, rho=1.0,
+                         condMin=0.1, difRcd=0.0, difTol=1e-5, itMax=10)
