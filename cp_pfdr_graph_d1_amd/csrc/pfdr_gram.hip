@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "pfdr_graph.hpp"
+#include "pfdr_power.hpp"
 #include "pfdr_quadratic_kernels.hpp"
 #include "pfdr_session.hpp"
 
@@ -765,11 +766,7 @@ template <typename real>
 __global__ void k_power_init(long n, int B, real *X) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * B) return;
-    unsigned long long z = (unsigned long long)i * 0xD1B54A32D192ED03ull + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    X[i] = (real)((double)(z >> 11) * (1.0 / 9007199254740992.0) * 2.0 - 1.0);
+    X[i] = (real)power_start_value((unsigned long long)i);
 }
 
 // per-column norms of X (n x B): one block per column
@@ -803,6 +800,13 @@ __global__ void k_power_step(int B, const real *__restrict__ a, real *b, int *st
     if ((a[c] - b[c]) / b[c] < nTol) { state[c] = 1; return; }
     b[c] = a[c];
     atomicAdd(running, 1);
+}
+
+template <typename real>
+void power_step(int B, const real *a, real *b, int *state, real nTol, int *running,
+                hipStream_t s) {
+    k_power_step<real><<<1, 64, 0, s>>>(B, a, b, state, nTol, running);
+    PFDR_HIP(hipGetLastError());
 }
 
 template <typename real>
@@ -1003,6 +1007,9 @@ static int gram_host(const char *fn, int which, int M, int N, const real *A, int
     return PFDR_OK;
 }
 
+template void power_step<float>(int, const float *, float *, int *, float, int *, hipStream_t);
+template void power_step<double>(int, const double *, double *, int *, double, int *,
+                                 hipStream_t);
 template void gram<float>(int, int, long, const float *, long, float *, hipStream_t);
 template void gram<double>(int, int, long, const double *, long, double *, hipStream_t);
 template float operator_norm_device<float>(int, int, const float *, float, int, int, int,

@@ -11,6 +11,7 @@
 #include "pfdr_quadratic_kernels.hpp"
 #include "pfdr_sort.hpp"
 #include "pfdr_sparse.hpp"
+#include "pfdr_sparse_view.hpp"
 
 namespace pfdr {
 
@@ -1971,6 +1972,30 @@ static int quadratic_host(const char *fn, int kind, int V, int E, int N, real *X
     p.itMax = itMax; p.verbose = verbose;
     return solve_one_call<QuadSession<real>>(fn, p, X, it, Obj, Dif, N, 1, !csc, csc);
 }
+
+// pfdr_sparse_view.hpp: a SparseOp set up as a session sets its own up, kept
+// by the owner handed back (the kernel family it chose is not used)
+template <typename real>
+std::shared_ptr<void> sparse_view(int N, int V, const pfdr_csc *A, int mem, hipStream_t s,
+                                  SparseView<real> &out) {
+    auto op = std::make_shared<SparseOp<real>>();
+    {
+        HostPins pins(s);
+        op->setup(V, N, A, mem, 0, s, pins);
+        pins.release();
+    }
+    out.N = N; out.V = V; out.nnz = op->nnz;
+    out.colptr = op->colptr.p; out.rowptr = op->rowptr.p;
+    out.rowidx = op->rowidx.p; out.colidx = op->colidx.p;
+    out.val = op->val.p; out.rval = op->rval.p;
+    out.maxcol = op->maxcol; out.maxrow = op->maxrow;
+    out.csr_ms = op->csr_ms;
+    return op;
+}
+template std::shared_ptr<void> sparse_view<float>(int, int, const pfdr_csc *, int, hipStream_t,
+                                                  SparseView<float> &);
+template std::shared_ptr<void> sparse_view<double>(int, int, const pfdr_csc *, int, hipStream_t,
+                                                   SparseView<double> &);
 
 }  // namespace pfdr
 

@@ -44,6 +44,8 @@ EXPORTED = (
     "pfdr_loss_d1_simplex_f32", "pfdr_loss_d1_simplex_f64",
     "pfdr_proj_simplex_metric_f32", "pfdr_proj_simplex_metric_f64",
     "pfdr_gram_f32", "pfdr_gram_f64", "pfdr_operator_norm_f32", "pfdr_operator_norm_f64",
+    "pfdr_operator_norm_csc_f32", "pfdr_operator_norm_csc_f64",
+    "pfdr_lipschitz_diag_csc_f32", "pfdr_lipschitz_diag_csc_f64",
     "pfdr_sequential_sum_f32", "pfdr_sequential_sum_f64",
     "pfdr_radix_sort_pairs_u32", "pfdr_radix_sort_pairs_u64",
     "pfdr_cp_reduce_f32", "pfdr_cp_reduce_f64",
@@ -218,6 +220,13 @@ def load():
                                        C.c_int, C.c_void_p]
         lib.pfdr_comm_destroy.argtypes = [C.c_void_p]
         vp = C.c_void_p
+        for sfx, ct in (("f32", C.c_float), ("f64", C.c_double)):
+            if hasattr(lib, "pfdr_operator_norm_csc_" + sfx):  # (as for the solver below)
+                getattr(lib, "pfdr_operator_norm_csc_" + sfx).argtypes = [
+                    C.c_int, C.c_int, C.POINTER(CSCStruct), C.c_int, ct, C.c_int, C.c_int,
+                    C.c_int, C.c_void_p, C.c_void_p]
+                getattr(lib, "pfdr_lipschitz_diag_csc_" + sfx).argtypes = [
+                    C.c_int, C.c_int, C.POINTER(CSCStruct), C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(lib, "pfdr_cp_solver_create"):  # (absent from an older PFDR_LIB_PATH build)
             _solver_argtypes(lib, vp)
         # (PFDR_LIB_PATH: an A/B against a build of the previous ABI, 3, which
@@ -944,7 +953,7 @@ def _binding_inputs(obs, source, target, edge_weight, A, l1_weight):
 
 def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0,
                       PFDR_rho=1.0, PFDR_condMin=1e-3, PFDR_difRcd=0.0, PFDR_difTol=1e-4,
-                      PFDR_itMax=10000, verbose=0):
+                      PFDR_itMax=10000, verbose=0, lipschitz="bound"):
     """PFDR front-end with the conventions of the reference's Python binding
     (python/CP_quadratic_l1_py.cpp:7-56, 130-258, which wraps CP; this
     entry solves the same functional F(x) = 1/2 ||A x - obs||^2 + sum_e
@@ -952,9 +961,12 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
       * A scalar -> identity (its value discarded); A of shape (N,) ->
         diagonal, obs and A pre-multiplied (obs*A, A*A) as the binding does
         (:121-132); A of shape (N, V) -> the design matrix; a CSC -> the
-        sparse design matrix, with the Lipschitz bound ||A||_1 ||A||_inf >=
-        ||A||^2 (largest absolute column sum times largest absolute row sum)
-        in place of the dense matrix's power iteration;
+        sparse design matrix, its Lipschitz information chosen by
+        ``lipschitz`` (read for a CSC only): "bound", the default, the scalar
+        ||A||_1 ||A||_inf >= ||A||^2 (largest absolute column sum times
+        largest absolute row sum); "power", the scalar operator_norm(csc) at
+        the dense path's settings (nTol 1e-3, itMax 100, nbInit 10); "diag",
+        the diagonal metric lipschitz_diag(csc)[0];
       * edge_weight / l1_weight: array, or scalar broadcast to every edge /
         vertex (the binding's broadcast loops run to V for both, :134-145,
         an out-of-range write for the edge weights when E > V; here each
@@ -964,6 +976,8 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
       * defaults from :64-72 (PFDR_rho 1, condMin 1e-3, difRcd 0, difTol
         1e-4, itMax 1e4).
     Returns (x, iterations)."""
+    if lipschitz not in ("bound", "power", "diag"):
+        raise ValueError('lipschitz must be "bound", "power" or "diag", got %r' % (lipschitz,))
     dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
                                                              A, l1_weight)
     lib = Lib()
@@ -980,10 +994,17 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
                                           PFDR_itMax, verbose=verbose)
     elif mode == "sparse":
         h = A.to_host()
-        a = np.abs(h.val.astype(np.float64))
-        cols = np.repeat(np.arange(h.V), np.diff(h.colptr))
-        L = np.array([np.bincount(cols, a, h.V).max() * np.bincount(h.rowidx, a, h.N).max()], dt)
-        X, it, _, _ = lib.quadratic_d1_l1(X0, obs, h, N, Eu, Ev, ew, lw, positivity, SCAL, L,
+        Ltype = SCAL
+        if lipschitz == "power":
+            L = np.array([operator_norm(A)[0]], dt)
+        elif lipschitz == "diag":
+            L, Ltype = lipschitz_diag(h)[0], DIAG
+        else:
+            a = np.abs(h.val.astype(np.float64))
+            cols = np.repeat(np.arange(h.V), np.diff(h.colptr))
+            L = np.array([np.bincount(cols, a, h.V).max() *
+                          np.bincount(h.rowidx, a, h.N).max()], dt)
+        X, it, _, _ = lib.quadratic_d1_l1(X0, obs, h, N, Eu, Ev, ew, lw, positivity, Ltype, L,
                                           PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
                                           PFDR_itMax, verbose=verbose)
     else:
@@ -1360,8 +1381,19 @@ def operator_norm(A, nTol=1e-3, itMax=100, nbInit=10, symmetric=False, device=Fa
     """||A||^2 (reference operator_norm_matrix).  symmetric=True: A is the
     S-by-S A^tA / AA^t itself (the reference's M or N = 0).  device=True: A
     is a torch CUDA tensor, column-major M-by-N stored as (N, M).  Returns
-    (norm2, gram_ms)."""
+    (norm2, gram_ms).  A CSC (host arrays or torch GPU tensors) goes through
+    pfdr_operator_norm_csc_*, the power method on the stored entries, and
+    returns (norm2, ms_power); symmetric, device, M and N do not apply."""
     lib = load()
+    if isinstance(A, CSC):
+        ct, sfx, _ = _real(A.dtype)
+        if A.device:
+            _producers_done()
+        csc, out, ms = A.struct(), ct(0), (C.c_double * 2)()
+        _check(getattr(lib, "pfdr_operator_norm_csc_" + sfx)(
+            A.N, A.V, C.byref(csc), PFDR_MEM_DEVICE if A.device else PFDR_MEM_HOST, ct(nTol),
+            itMax, nbInit, verbose, C.byref(out), ms), "pfdr_operator_norm_csc")
+        return out.value, ms[1]
     gms = C.c_double(0.0)
     if device:
         import torch
@@ -1385,6 +1417,30 @@ def operator_norm(A, nTol=1e-3, itMax=100, nbInit=10, symmetric=False, device=Fa
                                                       verbose, C.byref(out), C.byref(gms)),
            "pfdr_operator_norm")
     return out.value, gms.value
+
+
+def lipschitz_diag(csc):
+    """The diagonal Lipschitz majorant of a CSC (pfdr_lipschitz_diag_csc_*):
+    L[v] = sum_i |A_iv| sum_j |A_ij|, valid ``Ltype = DIAG`` input, and the
+    scalar bound ||A||_1 ||A||_inf >= max L.  Returns (L, bound): L a numpy
+    array, or a torch tensor beside a device CSC's arrays."""
+    if not isinstance(csc, CSC):
+        raise TypeError("lipschitz_diag takes a pfdr.CSC")
+    lib = load()
+    ct, sfx, _ = _real(csc.dtype)
+    st, bound = csc.struct(), ct(0)
+    if csc.device:
+        import torch
+        _producers_done()
+        L = torch.empty(max(csc.V, 0), dtype=csc.val.dtype, device=csc.val.device)
+        ptr, mem = L.data_ptr(), PFDR_MEM_DEVICE
+    else:
+        L = np.empty(max(csc.V, 0), csc.dtype)
+        ptr, mem = L.ctypes.data, PFDR_MEM_HOST
+    _check(getattr(lib, "pfdr_lipschitz_diag_csc_" + sfx)(
+        csc.N, csc.V, C.byref(st), mem, C.c_void_p(ptr), C.byref(bound)),
+        "pfdr_lipschitz_diag_csc")
+    return L, csc.dtype.type(bound.value)
 
 
 def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normItMax=100,

@@ -430,6 +430,41 @@ int pfdr_operator_norm_f32(int M, int N, const float *A, int mem, float nTol, in
                            int nbInit, int verbose, float *norm2, double *gram_ms);
 int pfdr_operator_norm_f64(int M, int N, const double *A, int mem, double nTol, int itMax,
                            int nbInit, int verbose, double *norm2, double *gram_ms);
+/* The same for A (N-by-V) in CSC (pfdr_csc above; its arrays host or device
+ * per mem, copied in and checked as pfdr_session_create_sparse checks them,
+ * except that an empty column is accepted): ||A||^2 by the power method on
+ * A^tA, two sparse products per iteration, never densified and never
+ * symmetrised.  All starts run at once in a batch of 16, 32 or 64, each with
+ * the reference's stopping rule (a - b)/b < nTol; the result is the largest b
+ * over the first nbInit starts (nbInit <= 0 counts as 1; a NaN never wins; a
+ * matrix whose stored values are all zero gives 0).  Start c, coordinate r,
+ * takes the dense entry's starting value number r + c V, c counting across
+ * batches.  Every sum adds its terms in a fixed order that depends on neither
+ * the batch size nor the other starts, and there are no floating-point
+ * atomics: a start's result does not depend on nbInit, and two calls give the
+ * same bytes.  A negative itMax runs no iteration after the first product, as
+ * in the dense entry.  ms (may be NULL) receives two values: the wall time of
+ * the CSR build and of the power method.
+ *
+ * PFDR_ERR_ARG, naming the offence and before any device work: N <= 0,
+ * V <= 0, mem neither PFDR_MEM_HOST nor _DEVICE, a NULL pfdr_csc or array in
+ * it, nnz outside [1, 2^31 - 256), a NULL norm2; after the one-pass device
+ * check and before any product: a malformed colptr or rowidx. */
+int pfdr_operator_norm_csc_f32(int N, int V, const pfdr_csc *A, int mem, float nTol, int itMax,
+                               int nbInit, int verbose, float *norm2, double *ms);
+int pfdr_operator_norm_csc_f64(int N, int V, const pfdr_csc *A, int mem, double nTol, int itMax,
+                               int nbInit, int verbose, double *norm2, double *ms);
+/* The diagonal Lipschitz majorant of a CSC: L[v] = sum_i |A_iv| r_i with
+ * r_i = sum_j |A_ij| (V values, host or device per mem).  By Cauchy-Schwarz
+ * A^tA <= diag(L), so L is valid PFDR_LIPSCHITZ_DIAG input, and max_v L[v] <=
+ * ||A||_1 ||A||_inf.  *bound (a host value, may be NULL) receives that scalar
+ * bound, max_v sum_i |A_iv| times max_i r_i.  Every sum runs over the stored
+ * entries in stored order, in double, and is rounded once to the real type.
+ * An empty column gives L[v] = 0 (the sessions refuse such a column anyway:
+ * its squared norm is 0).  Arguments and errors as above (L for norm2). */
+int pfdr_lipschitz_diag_csc_f32(int N, int V, const pfdr_csc *A, int mem, float *L, float *bound);
+int pfdr_lipschitz_diag_csc_f64(int N, int V, const pfdr_csc *A, int mem, double *L,
+                                double *bound);
 
 /* Cut-pursuit reduced-problem builder (reference
  * src/CP_PFDR_graph_quadratic_d1_l1.cpp:663-841).
