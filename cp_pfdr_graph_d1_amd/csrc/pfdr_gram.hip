@@ -761,12 +761,14 @@ __global__ __launch_bounds__(256) void k_apply_cols(int rows, long cols, const r
     }
 }
 
-// starting vectors: U[-1, 1) from splitmix64 (deterministic)
+// starting vectors: U[-1, 1) from splitmix64 (deterministic); column cl of the
+// batch is start c = c0 + cl, numbered across batches as k_spn_init numbers them
 template <typename real>
-__global__ void k_power_init(long n, int B, real *X) {
+__global__ void k_power_init(long n, int B, int c0, real *X) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * B) return;
-    X[i] = (real)power_start_value((unsigned long long)i);
+    X[i] = (real)power_start_value((unsigned long long)i +
+                                   (unsigned long long)c0 * (unsigned long long)n);
 }
 
 // per-column norms of X (n x B): one block per column
@@ -899,7 +901,7 @@ real operator_norm_device(int M, int N, const real *A, real nTol, int itMax, int
         DevBuf<real> X((size_t)n * B), Y((size_t)n * B), T(sym ? 0 : (size_t)M * B), a(B), b(B);
         DevBuf<int> state(B), running(1);
         PFDR_HIP(hipMemsetAsync(state.p, 0, B * sizeof(int), s));
-        k_power_init<real><<<grid_for((long)n * B), kBlock, 0, s>>>(n, B, X.p);
+        k_power_init<real><<<grid_for((long)n * B), kBlock, 0, s>>>(n, B, done, X.p);
         auto apply = [&](real *in, real *out) {  // out = Mat^t Mat in (or Mat in)
             if (sym) {
                 apply_rows<real>(B, n, n, Mat, n, in, out, s);

@@ -5,9 +5,9 @@
 
 namespace pfdr {
 
-// Starting value number i: U[-1, 1) from splitmix64 (deterministic).  The
-// dense entry numbers a batch's values i = r + c n (coordinate r of start c,
-// vectors of length n).
+// Starting value number i: U[-1, 1) from splitmix64 (deterministic).  Both
+// entries number their values i = r + c n (coordinate r of start c, vectors of
+// length n), c counted across batches: start c is the same vector in any batch.
 __device__ __forceinline__ double power_start_value(unsigned long long i) {
     unsigned long long z = i * 0xD1B54A32D192ED03ull + 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

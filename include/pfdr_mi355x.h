@@ -424,7 +424,8 @@ int pfdr_radix_sort_pairs_u32(int64_t n, uint32_t *keys, uint32_t *vals, int bit
 int pfdr_radix_sort_pairs_u64(int64_t n, uint64_t *keys, uint32_t *vals, int bits, double *ms);
 /* Squared operator norm ||A||^2 by the power method (reference
  * operator_norm_matrix<real>, include/operator_norm_matrix.hpp:12-14, same
- * argument meaning; deterministic starts).  *gram_ms (may be NULL): time of
+ * argument meaning; deterministic starts, numbered across the batches of 64
+ * that nbInit > 64 takes).  *gram_ms (may be NULL): time of
  * the Gram step when the matrix was symmetrised first. */
 int pfdr_operator_norm_f32(int M, int N, const float *A, int mem, float nTol, int itMax,
                            int nbInit, int verbose, float *norm2, double *gram_ms);

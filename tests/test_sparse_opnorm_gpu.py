@@ -5,10 +5,13 @@ The yardsticks are numpy's: ||A||_2^2 from the SVD of the float64 matrix, at
 the settings and tolerances of tests/test_gram_gpu.py's
 test_operator_norm_matches_svd (nTol 1e-6, nbInit 10, relative error <= 1e-4
 in f32 and <= 1e-5 in f64), and the float64 formula of the metric.  All
-matrices are non-negative with a spectral gap sigma_2^2 / sigma_1^2 <= 0.48; a
-numpy restatement of the batched power method with the same starts is within
-2.1e-6 (f32) and 3.0e-7 (f64) of the SVD on every one of them, so the
-tolerances leave the algorithm itself a margin of 30x and more.
+matrices are non-negative with a spectral gap sigma_2^2 / sigma_1^2 <= 0.48; the
+numpy restatement of the batched power method with the same starts
+(tests/power_twin.py, run on these matrices by tests/test_power_twin_cpu.py's
+test_twin_matches_svd) is within 2.1e-6 (f32) and 3.0e-7 (f64) of the SVD on
+every one of them, so the tolerances leave the algorithm itself a margin of
+30x and more.  tests/test_power_method_gpu.py holds the entries to that
+restatement's bytes, start by start, on signed matrices.
 """
 import functools
 
