@@ -18,12 +18,18 @@
 // A sparse A (N > 0, pfdr_cp_reduce_csc_*) changes the column-sum step only:
 // rA comes from the stored entries (pfdr_cp_sparse.hip) with the bytes of
 // k_cp_colsum on the densified matrix, and the rest runs on it as it is.
+// pfdr_cp_reduce_csc_sparse_* (cp_reduce_sparse_direct) keeps rA sparse
+// through the direct branch: column norms, the equilibration round trip, the
+// CSC power method and L on the stored entries, the dense steps' bytes but
+// for c, which comes from another power method.
 #include <cmath>
 #include <stdexcept>
+#include <string>
 
 #include "pfdr_cp_sparse.hpp"
 #include "pfdr_graph.hpp"
 #include "pfdr_session.hpp"
+#include "pfdr_sparse_view.hpp"
 
 namespace pfdr {
 
@@ -323,7 +329,108 @@ static int cp_reduce_csc(const char *fn, int N, int V, const pfdr_csc *A, const 
                                 normNbInit, rA, rAA, rY, L, Leq, &sp);
 }
 
+// The direct branch above (:801-839) on the stored entries of a sparse rA:
+// every step skips the +-0 terms of the dense one and so gives its bytes.
+template <typename real>
+long cp_reduce_sparse_direct(CpCsc<real> &A, int rV, const int *rVc, const int *Vc, real normTol,
+                             int normItMax, int normNbInit, CpReduced<real> &rA, real *l, real *L,
+                             hipStream_t s) {
+    A.reduced(rV, rVc, Vc, rA, s);
+    const long bad = rA.colnorm(l, s);
+    if (bad >= 0) return bad;
+    rA.scale(l, 0, s);
+    SparseView<real> view;
+    view.N = rA.N, view.V = rV, view.nnz = rA.rnnz;
+    view.colptr = rA.colptr.p, view.rowidx = rA.rowidx.p, view.val = rA.val.p;
+    view.rowptr = rA.rowptr.p, view.colidx = rA.colidx.p, view.rval = rA.rval.p;
+    const real c = operator_norm_sparse<real>(view, normTol, normItMax, normNbInit, 0, s);
+    rA.scale(l, 1, s);
+    k_cp_lipschitz<real><<<grid_for(rV), kBlock, 0, s>>>(rV, l, c, L);
+    PFDR_HIP(hipGetLastError());
+    PFDR_HIP(hipStreamSynchronize(s));  // as cp_reduce_host: a session need not run on s
+    return -1;
+}
+template long cp_reduce_sparse_direct<float>(CpCsc<float> &, int, const int *, const int *, float,
+                                             int, int, CpReduced<float> &, float *, float *,
+                                             hipStream_t);
+template long cp_reduce_sparse_direct<double>(CpCsc<double> &, int, const int *, const int *,
+                                              double, int, int, CpReduced<double> &, double *,
+                                              double *, hipStream_t);
+
+// the public entry of the direct branch with rA returned as a CSC
+template <typename real>
+static int cp_reduce_csc_sparse(const char *fn, int N, int V, const pfdr_csc *A, const real *Y,
+                                int rV, const int *rVc, const int *Vc, int mem, real normTol,
+                                int normItMax, int normNbInit, int64_t *rnnz, int64_t *rcolptr,
+                                int32_t *rrowidx, real *rval, real *L, real *Leq) {
+    if (N <= 0) return report_error(fn, "a sparse A needs N > 0");
+    if (V <= 0 || (mem != PFDR_MEM_HOST && mem != PFDR_MEM_DEVICE))
+        return report_error(fn, "invalid arguments");
+    if (const char *bad = cp_csc_args(A)) return report_error(fn, bad);
+    if (rV <= 0 || rV > V || !Y || !rVc || !Vc) return report_error(fn, "invalid arguments");
+    if (!rnnz || !rcolptr || !rrowidx || !rval)
+        return report_error(fn, "rnnz, rcolptr, rrowidx and rval are required");
+    try {
+        hipStream_t s = lib_stream();
+        const bool dev = mem == PFDR_MEM_DEVICE;
+        CpCsc<real> sp;
+        sp.take(N, V, A, mem, s);
+        DevBuf<int> bptr, bVc;
+        const int *dptr = rVc, *dVc = Vc;
+        if (!dev) {
+            bptr.alloc(rV + 1);
+            bVc.alloc(V);
+            PFDR_HIP(hipMemcpyAsync(bptr.p, rVc, (rV + 1) * 4, hipMemcpyHostToDevice, s));
+            PFDR_HIP(hipMemcpyAsync(bVc.p, Vc, (size_t)V * 4, hipMemcpyHostToDevice, s));
+            dptr = bptr.p;
+            dVc = bVc.p;
+        }
+        CpReduced<real> r;
+        DevBuf<real> l(rV), dL(rV);
+        const long bad = cp_reduce_sparse_direct<real>(sp, rV, dptr, dVc, normTol, normItMax,
+                                                       normNbInit, r, l.p, dL.p, s);
+        if (bad >= 0) {
+            const std::string msg = "reduced column " + std::to_string(bad) +
+                                    " has norm 0 (or not finite): a sparse reduced operator "
+                                    "needs every column's norm positive";
+            return report_error(fn, msg.c_str());
+        }
+        const auto k = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        *rnnz = r.rnnz;
+        PFDR_HIP(hipMemcpyAsync(rcolptr, r.colptr.p, ((size_t)rV + 1) * 8, k, s));
+        PFDR_HIP(hipMemcpyAsync(rrowidx, r.rowidx.p, (size_t)r.rnnz * 4, k, s));
+        PFDR_HIP(hipMemcpyAsync(rval, r.val.p, (size_t)r.rnnz * sizeof(real), k, s));
+        if (L) PFDR_HIP(hipMemcpyAsync(L, dL.p, rV * sizeof(real), k, s));
+        if (Leq) PFDR_HIP(hipMemcpyAsync(Leq, l.p, rV * sizeof(real), k, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+    } catch (const HipError &h) {
+        return report_error(fn, h);
+    } catch (const std::exception &ex) {
+        return report_error(fn, ex.what());
+    }
+    return PFDR_OK;
+}
+
 }  // namespace pfdr
+
+extern "C" int pfdr_cp_reduce_csc_sparse_f32(int N, int V, const pfdr_csc *A, const float *Y,
+                                             int rV, const int *rVc, const int *Vc, int mem,
+                                             float normTol, int normItMax, int normNbInit,
+                                             int64_t *rnnz, int64_t *rcolptr, int32_t *rrowidx,
+                                             float *rval, float *L, float *Leq) {
+    return pfdr::cp_reduce_csc_sparse<float>("pfdr_cp_reduce_csc_sparse_f32", N, V, A, Y, rV, rVc,
+                                             Vc, mem, normTol, normItMax, normNbInit, rnnz,
+                                             rcolptr, rrowidx, rval, L, Leq);
+}
+extern "C" int pfdr_cp_reduce_csc_sparse_f64(int N, int V, const pfdr_csc *A, const double *Y,
+                                             int rV, const int *rVc, const int *Vc, int mem,
+                                             double normTol, int normItMax, int normNbInit,
+                                             int64_t *rnnz, int64_t *rcolptr, int32_t *rrowidx,
+                                             double *rval, double *L, double *Leq) {
+    return pfdr::cp_reduce_csc_sparse<double>("pfdr_cp_reduce_csc_sparse_f64", N, V, A, Y, rV,
+                                              rVc, Vc, mem, normTol, normItMax, normNbInit, rnnz,
+                                              rcolptr, rrowidx, rval, L, Leq);
+}
 
 extern "C" int pfdr_cp_reduce_csc_f32(int N, int V, const pfdr_csc *A, const float *Y, int rV,
                                       const int *rVc, const int *Vc, int preAt, int mem,

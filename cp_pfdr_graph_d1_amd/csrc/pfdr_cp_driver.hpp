@@ -76,6 +76,13 @@ struct CpDriverBase {
     // N > 0, p.A null): the observation operator in CSC, arrays per p.mem;
     // setup() copies it, and nothing reads the pointer afterwards.
     const pfdr_csc *sparse = nullptr;
+    // pfdr_cp_solver_set_reduced: how a quadratic driver that holds a sparse A
+    // keeps the reduced operator of a direct iteration (PFDR_REDUCED_*), and
+    // what the last loop did: iterations solved on a sparse rA, direct
+    // iterations solved on a dense one, the most entries a sparse rA stored.
+    int reduced = PFDR_REDUCED_DENSE;
+    int64_t sparse_its = 0, dense_direct_its = 0, max_rnnz = 0;
+    virtual bool holds_sparse_A() const { return false; }
 
     // p.mem = PFDR_MEM_DEVICE: the arrays are device memory, copied except A,
     // which is borrowed.  want_obj: evaluate the functional at the initial state.
@@ -134,11 +141,14 @@ struct CpSeqSum {
     }
 };
 
-// One reduced problem: a PFDR session on p, run to its end; its iterate
-// (bytes of it) replaces p.X.  Returns PFDR_it.
-inline int cp_pfdr_solve(const pfdr_problem &p, size_t bytes, hipStream_t s) {
+// One reduced problem: a PFDR session on p (A: a sparse session on this
+// matrix, p.A null), run to its end; its iterate (bytes of it) replaces p.X.
+// Returns PFDR_it.
+inline int cp_pfdr_solve(const pfdr_problem &p, size_t bytes, hipStream_t s,
+                         const pfdr_csc *A = nullptr) {
     pfdr_session *ses = nullptr;
-    CP_ABI(pfdr_session_create(&ses, &p));
+    if (A) CP_ABI(pfdr_session_create_sparse(&ses, &p, A));
+    else CP_ABI(pfdr_session_create(&ses, &p));
     struct Hold {
         pfdr_session *q;
         ~Hold() { pfdr_session_destroy(q); }
@@ -151,6 +161,13 @@ inline int cp_pfdr_solve(const pfdr_problem &p, size_t bytes, hipStream_t s) {
     PFDR_HIP(hipMemcpyAsync(p.X, x, bytes, hipMemcpyDeviceToDevice, s));
     PFDR_HIP(hipStreamSynchronize(s));
     return pit;
+}
+
+// The same for a reduced operator kept sparse: p.A is null and A (device
+// arrays) takes its place.
+inline int cp_pfdr_solve_sparse(const pfdr_problem &p, const pfdr_csc &A, size_t bytes,
+                                hipStream_t s) {
+    return cp_pfdr_solve(p, bytes, s, &A);
 }
 
 // Cv and n component values to the host

@@ -485,6 +485,29 @@ extern "C" int pfdr_cp_solver_set_penalties(pfdr_cp_solver *h, const void *La_d1
     })
 }
 
+extern "C" int pfdr_cp_solver_set_reduced(pfdr_cp_solver *h, int mode) {
+    const char *fn = "pfdr_cp_solver_set_reduced";
+    if (!h) return report_error(fn, "invalid arguments");
+    if (h->kind == PFDR_KIND_SIMPLEX)
+        return report_error(fn, "the simplex kind has no reduced operator");
+    if (!h->d->holds_sparse_A())
+        return report_error(fn, "the solver was not created by pfdr_cp_solver_create_sparse");
+    if (mode != PFDR_REDUCED_DENSE && mode != PFDR_REDUCED_SPARSE)
+        return report_error(fn, "mode must be PFDR_REDUCED_DENSE or PFDR_REDUCED_SPARSE");
+    h->d->reduced = mode;
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_cp_solver_reduced_stats(pfdr_cp_solver *h, int64_t *sparse_iterations,
+                                            int64_t *dense_direct_iterations,
+                                            int64_t *max_rnnz) {
+    if (!h) return report_error("pfdr_cp_solver_reduced_stats", "invalid arguments");
+    if (sparse_iterations) *sparse_iterations = h->d->sparse_its;
+    if (dense_direct_iterations) *dense_direct_iterations = h->d->dense_direct_its;
+    if (max_rnnz) *max_rnnz = h->d->max_rnnz;
+    return PFDR_OK;
+}
+
 extern "C" int pfdr_cp_solver_stats(pfdr_cp_solver *h, double *seconds, int64_t *counts,
                                     double *setup_seconds) {
     if (!h) return report_error("pfdr_cp_solver_stats", "invalid arguments");

@@ -13,6 +13,20 @@
 // Integer work and one writer per element: the same bytes on every run.  A
 // run of any length is walked by its one lane.
 //
+// The reduced operator kept sparse (CpCsc::reduced -> CpReduced).  Steps 1
+// and 2 as above; then
+//   3'. a scan of the run-head flags numbers the runs h = 0 .. rnnz - 1 in the
+//       sorted order (rows ascending, and inside a row the components
+//       ascending, since a component's positions are one range of Vc); the
+//       head's lane adds its run as in 3 and stores (component, sum) at h:
+//       the CSR view, its row offsets written by the head that opens a row;
+//   4'. the pairs (component, h) are sorted by component, stably, so a
+//       column's rows ascend strictly: the CSC.
+// A run is stored whatever its sum (a cancellation is a stored zero), so the
+// structure depends on A's structure and the partition only.  The column
+// norms, the scaling and the residual on a CpReduced walk stored entries in
+// the dense kernels' order (k_cp_colnorm, k_cp_scale_cols, k_cpq_residual).
+//
 // Gradient: one lane per column, products formed, then added in stored order.
 #include <algorithm>
 #include <stdexcept>
@@ -59,26 +73,41 @@ __global__ __launch_bounds__(256) void k_cpsp_check(int V, int N, int64_t nnz,
     if (bad) atomicOr(word, bad);
 }
 
-// ---- the scan of the column lengths in Vc order: positions 0 .. V, 16 per
-// lane, a chunk of 4096 per workgroup
+// ---- an exclusive scan of len(0), len(1), ... over the positions 0 .. n
+// (len = 0 from n on), 16 per lane, a chunk of 4096 per workgroup.  Two
+// lengths: the columns in Vc order, and the run heads of the sorted entries.
 constexpr int kPer = 16, kChunk = kBlock * kPer;
 
 // stored entries of the column at position i (none at i = V, or for a vertex outside [0, V))
-__device__ __forceinline__ int64_t cpsp_len(int V, const int64_t *__restrict__ colptr,
-                                            const int *__restrict__ Vc, long i) {
-    if (i >= V) return 0;
-    const int v = Vc ? Vc[i] : (int)i;
-    if ((unsigned)v >= (unsigned)V) return 0;
-    return colptr[v + 1] - colptr[v];
-}
+struct CpspColLen {
+    int V;
+    const int64_t *colptr;
+    const int *Vc;
+    __device__ __forceinline__ int64_t operator()(long i) const {
+        if (i >= V) return 0;
+        const int v = Vc ? Vc[i] : (int)i;
+        if ((unsigned)v >= (unsigned)V) return 0;
+        return colptr[v + 1] - colptr[v];
+    }
+};
 
-__global__ __launch_bounds__(256) void k_cpsp_chunk_sums(int V, const int64_t *__restrict__ colptr,
-                                                         const int *__restrict__ Vc,
-                                                         int64_t *__restrict__ sums) {
+// 1 where sorted entry p opens a (row, component) run
+struct CpspRunHead {
+    int64_t nnz;
+    const unsigned *rows;
+    const int *sc;
+    __device__ __forceinline__ int64_t operator()(long p) const {
+        if (p >= nnz) return 0;
+        return p == 0 || rows[p - 1] != rows[p] || sc[p - 1] != sc[p];
+    }
+};
+
+template <typename Len>
+__global__ __launch_bounds__(256) void k_cpsp_chunk_sums(Len len, int64_t *__restrict__ sums) {
     __shared__ int64_t part[kBlock];
     const long i0 = (long)blockIdx.x * kChunk + (long)threadIdx.x * kPer;
     int64_t a = 0;
-    for (int k = 0; k < kPer; k++) a += cpsp_len(V, colptr, Vc, i0 + k);
+    for (int k = 0; k < kPer; k++) a += len(i0 + k);
     part[threadIdx.x] = a;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -99,8 +128,9 @@ __global__ void k_cpsp_scan_sums(int nc, int64_t *__restrict__ sums) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_cpsp_chunk_scan(int V, const int64_t *__restrict__ colptr,
-                                                         const int *__restrict__ Vc,
+// off[i] = len(0) + ... + len(i - 1), i = 0 .. n
+template <typename Len>
+__global__ __launch_bounds__(256) void k_cpsp_chunk_scan(long n, Len lenf,
                                                          const int64_t *__restrict__ sums,
                                                          int64_t *__restrict__ off) {
     __shared__ int64_t part[kBlock];
@@ -108,7 +138,7 @@ __global__ __launch_bounds__(256) void k_cpsp_chunk_scan(int V, const int64_t *_
     int64_t len[kPer], a = 0;
 #pragma unroll
     for (int k = 0; k < kPer; k++) {
-        len[k] = cpsp_len(V, colptr, Vc, i0 + k);
+        len[k] = lenf(i0 + k);
         a += len[k];
     }
     part[threadIdx.x] = a;
@@ -125,9 +155,18 @@ __global__ __launch_bounds__(256) void k_cpsp_chunk_scan(int V, const int64_t *_
     int64_t run = sums[blockIdx.x] + part[threadIdx.x];
 #pragma unroll
     for (int k = 0; k < kPer; k++) {
-        if (i0 + k <= V) off[i0 + k] = run;
+        if (i0 + k <= n) off[i0 + k] = run;
         run += len[k];
     }
+}
+
+// off[0 .. n] on stream s; sums: (n + kChunk) / kChunk words of scratch
+template <typename Len>
+void cpsp_scan(long n, Len len, int64_t *sums, int64_t *off, hipStream_t s) {
+    const int nc = (int)((n + kChunk) / kChunk);  // chunks of the positions 0 .. n
+    k_cpsp_chunk_sums<Len><<<nc, kBlock, 0, s>>>(len, sums);
+    k_cpsp_scan_sums<<<1, kWave, 0, s>>>(nc, sums);
+    k_cpsp_chunk_scan<Len><<<nc, kBlock, 0, s>>>(n, len, sums, off);
 }
 
 // cv[Vc[i]] = the component whose range of Vc holds position i (rVc = nullptr: 0)
@@ -207,6 +246,136 @@ __global__ __launch_bounds__(256) void k_cpsp_runs(int64_t nnz, int N,
         q++;
     } while (q < nnz && rows[q] == r && sc[q] == c);
     rA[(size_t)N * c + r] = a;
+}
+
+// ---- the reduced operator kept sparse (CpReduced)
+// k_cpsp_runs with the sum stored at the run's number h = pos[p] instead of a
+// dense element: CSR column and value of entry h, its row, and the (component,
+// h) pair that the sort by component takes
+template <typename real>
+__global__ __launch_bounds__(256) void k_cpsp_runs_csr(int64_t nnz,
+                                                       const unsigned *__restrict__ rows,
+                                                       const int *__restrict__ sc,
+                                                       const real *__restrict__ sv,
+                                                       const int64_t *__restrict__ pos,
+                                                       int *__restrict__ colidx,
+                                                       real *__restrict__ rval,
+                                                       unsigned *__restrict__ hrow,
+                                                       unsigned *__restrict__ keys,
+                                                       unsigned *__restrict__ vals) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    const unsigned r = rows[p];
+    const int c = sc[p];
+    if (p > 0 && rows[p - 1] == r && sc[p - 1] == c) return;
+    real a = real(0);
+    int64_t q = p;
+    do {
+        a += sv[q];
+        q++;
+    } while (q < nnz && rows[q] == r && sc[q] == c);
+    const int64_t h = pos[p];
+    colidx[h] = c;
+    rval[h] = a;
+    hrow[h] = r;
+    keys[h] = (unsigned)c;
+    vals[h] = (unsigned)h;
+}
+
+// ptr[q] = the first of the n sorted ids that is >= q, q = 0 .. m: written by
+// the position that opens an id, and the tail by the last position
+__global__ __launch_bounds__(256) void k_cpsp_offsets(int64_t n, long m,
+                                                      const unsigned *__restrict__ id,
+                                                      int64_t *__restrict__ ptr) {
+    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n) return;
+    const long r = (long)id[h];
+    const long prev = h ? (long)id[h - 1] : -1L;
+    for (long q = prev + 1; q <= r && q <= m; q++) ptr[q] = h;
+    if (h == n - 1)
+        for (long q = r + 1; q <= m; q++) ptr[q] = n;
+}
+
+// the CSC from the heads sorted by component (comp[j], head[j])
+template <typename real>
+__global__ __launch_bounds__(256) void k_cpsp_csc_fill(int64_t n, const unsigned *__restrict__ comp,
+                                                       const unsigned *__restrict__ head,
+                                                       const unsigned *__restrict__ hrow,
+                                                       const real *__restrict__ rval,
+                                                       int *__restrict__ rowidx,
+                                                       int *__restrict__ ecol,
+                                                       real *__restrict__ val) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const unsigned h = head[j];
+    rowidx[j] = (int)hrow[h];
+    ecol[j] = (int)comp[j];
+    val[j] = rval[h];
+}
+
+// l[rv] = ||rA[:, rv]||, the stored squares added in ascending row order
+// (k_cp_colnorm without its +0 terms); *bad = the first rv with l 0 or not finite
+template <typename real>
+__global__ __launch_bounds__(256) void k_cpsp_colnorm(int rV, const int64_t *__restrict__ colptr,
+                                                      const real *__restrict__ val,
+                                                      real *__restrict__ l, int *__restrict__ bad) {
+    const int rv = blockIdx.x * blockDim.x + threadIdx.x;
+    if (rv >= rV) return;
+    real s = real(0);
+    for (int64_t e = colptr[rv], e1 = colptr[rv + 1]; e < e1; e++) {
+        const real b = val[e];
+        s += b * b;
+    }
+    const real x = std::sqrt(s);
+    l[rv] = x;
+    if (!(x > real(0)) || x - x != real(0)) atomicMin(bad, rv);
+}
+
+// val[e] /= (mul: *=) l[col[e]] (k_cp_scale_cols, element by element)
+template <typename real>
+__global__ __launch_bounds__(256) void k_cpsp_scale(int64_t n, const int *__restrict__ col,
+                                                    const real *__restrict__ l,
+                                                    real *__restrict__ val, int mul) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    if (mul) val[e] *= l[col[e]];
+    else val[e] /= l[col[e]];
+}
+
+// R[n] = Y[n] - sum of rval[e] rX[colidx[e]] over row n's entries, rv
+// ascending, each product formed and then added from +0 (k_cpq_residual
+// without its +-0 terms); one lane per row, 4 entries' loads in flight
+template <typename real>
+__global__ __launch_bounds__(256) void k_cpsp_residual(int N, const int64_t *__restrict__ rowptr,
+                                                       const int *__restrict__ colidx,
+                                                       const real *__restrict__ rval,
+                                                       const real *__restrict__ rX,
+                                                       const real *__restrict__ Y,
+                                                       real *__restrict__ R) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    int64_t e = rowptr[n];
+    const int64_t e1 = rowptr[n + 1];
+    constexpr int U = 4;
+    real a = real(0);
+    for (; e + U <= e1; e += U) {
+        real x[U], y[U];
+#pragma unroll
+        for (int q = 0; q < U; q++) {
+            x[q] = rval[e + q];
+            y[q] = rX[colidx[e + q]];
+        }
+#pragma unroll
+        for (int q = 0; q < U; q++) {
+            const real b = x[q] * y[q];
+            a += b;
+        }
+    }
+    for (; e < e1; e++) {
+        const real b = rval[e] * rX[colidx[e]];
+        a += b;
+    }
+    R[n] = Y[n] - a;
 }
 
 // DfS[v] = -(sum of val[e] R[rowidx[e]]), column v's entries in stored order;
@@ -289,7 +458,7 @@ void CpCsc<real>::take(int N_, int V_, const pfdr_csc *A, int mem, hipStream_t s
 }
 
 template <typename real>
-void CpCsc<real>::colsum(int rV, const int *rVc, const int *Vc, real *rA, hipStream_t s) {
+void CpCsc<real>::sort_entries(int rV, const int *rVc, const int *Vc, hipStream_t s) {
     if (!ki.p) {
         off.alloc((size_t)V + 1);
         sums.alloc(((size_t)V + kChunk) / kChunk);
@@ -298,12 +467,8 @@ void CpCsc<real>::colsum(int rV, const int *rVc, const int *Vc, real *rA, hipStr
         sv.alloc(nnz);
         ki.alloc(nnz), ko.alloc(nnz), vi.alloc(nnz), vo.alloc(nnz);
     }
-    const int nc = (int)sums.n;  // chunks of the positions 0 .. V
-    PFDR_HIP(hipMemsetAsync(rA, 0, sizeof(real) * (size_t)N * rV, s));
     PFDR_HIP(hipMemsetAsync(cv.p, 0, sizeof(int) * (size_t)V, s));
-    k_cpsp_chunk_sums<<<nc, kBlock, 0, s>>>(V, colptr.p, Vc, sums.p);
-    k_cpsp_scan_sums<<<1, kWave, 0, s>>>(nc, sums.p);
-    k_cpsp_chunk_scan<<<nc, kBlock, 0, s>>>(V, colptr.p, Vc, sums.p, off.p);
+    cpsp_scan(V, CpspColLen{V, colptr.p, Vc}, sums.p, off.p, s);
     k_cpsp_comp<<<grid_for(V), kBlock, 0, s>>>(V, rV, rVc, Vc, cv.p);
     k_cpsp_keys<<<grid_for(nnz), kBlock, 0, s>>>(V, nnz, off.p, colptr.p, Vc, rowidx.p, ki.p,
                                                  vi.p);
@@ -313,7 +478,76 @@ void CpCsc<real>::colsum(int rV, const int *rVc, const int *Vc, real *rA, hipStr
     radix_sort_pairs_stable<unsigned>(ki.p, ko.p, vi.p, vo.p, (long)nnz, bits, s);
     k_cpsp_gather<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, vo.p, ecol.p, cv.p, val.p, sv.p,
                                                          sc.p);
+    PFDR_HIP(hipGetLastError());
+}
+
+template <typename real>
+void CpCsc<real>::colsum(int rV, const int *rVc, const int *Vc, real *rA, hipStream_t s) {
+    PFDR_HIP(hipMemsetAsync(rA, 0, sizeof(real) * (size_t)N * rV, s));
+    sort_entries(rV, rVc, Vc, s);
     k_cpsp_runs<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, N, ko.p, sc.p, sv.p, rA);
+    PFDR_HIP(hipGetLastError());
+}
+
+template <typename real>
+void CpCsc<real>::reduced(int rV, const int *rVc, const int *Vc, CpReduced<real> &out,
+                          hipStream_t s) {
+    sort_entries(rV, rVc, Vc, s);
+    if (!pos.p) {
+        pos.alloc((size_t)nnz + 1);
+        psums.alloc(((size_t)nnz + kChunk) / kChunk);
+        hrow.alloc(nnz);
+    }
+    // the run heads before every sorted entry; their count comes back
+    cpsp_scan((long)nnz, CpspRunHead{nnz, ko.p, sc.p}, psums.p, pos.p, s);
+    PFDR_HIP(hipGetLastError());
+    int64_t rnnz = 0;
+    PFDR_HIP(hipMemcpyAsync(&rnnz, pos.p + nnz, sizeof rnnz, hipMemcpyDeviceToHost, s));
+    PFDR_HIP(hipStreamSynchronize(s));
+    out.N = N, out.rV = rV, out.rnnz = rnnz;
+    out.rowptr.alloc((size_t)N + 1);
+    out.colptr.alloc((size_t)rV + 1);
+    out.colidx.alloc(rnnz), out.rval.alloc(rnnz);
+    out.rowidx.alloc(rnnz), out.ecol.alloc(rnnz), out.val.alloc(rnnz);
+    // CSR: the heads in sorted order (rows ascending, components ascending inside a row)
+    k_cpsp_runs_csr<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, ko.p, sc.p, sv.p, pos.p,
+                                                           out.colidx.p, out.rval.p, hrow.p, ki.p,
+                                                           vi.p);
+    k_cpsp_offsets<<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, N, hrow.p, out.rowptr.p);
+    PFDR_HIP(hipGetLastError());
+    // CSC: the heads sorted by component, stably, so that a column's rows ascend
+    int bits = 1;
+    while (bits < 32 && (1L << bits) < (long)rV) bits++;
+    radix_sort_pairs_stable<unsigned>(ki.p, ko.p, vi.p, vo.p, (long)rnnz, bits, s);
+    k_cpsp_csc_fill<real><<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, ko.p, vo.p, hrow.p, out.rval.p,
+                                                            out.rowidx.p, out.ecol.p, out.val.p);
+    k_cpsp_offsets<<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, rV, ko.p, out.colptr.p);
+    PFDR_HIP(hipGetLastError());
+}
+
+template <typename real>
+long CpReduced<real>::colnorm(real *l, hipStream_t s) const {
+    DevBuf<int> bad(1);
+    const int none = 0x7fffffff;
+    int first = none;
+    PFDR_HIP(hipMemcpyAsync(bad.p, &none, sizeof none, hipMemcpyHostToDevice, s));
+    k_cpsp_colnorm<real><<<grid_for(rV), kBlock, 0, s>>>(rV, colptr.p, val.p, l, bad.p);
+    PFDR_HIP(hipGetLastError());
+    PFDR_HIP(hipMemcpyAsync(&first, bad.p, sizeof first, hipMemcpyDeviceToHost, s));
+    PFDR_HIP(hipStreamSynchronize(s));
+    return first == none ? -1L : (long)first;
+}
+
+template <typename real>
+void CpReduced<real>::scale(const real *l, int mul, hipStream_t s) {
+    k_cpsp_scale<real><<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, ecol.p, l, val.p, mul);
+    k_cpsp_scale<real><<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, colidx.p, l, rval.p, mul);
+    PFDR_HIP(hipGetLastError());
+}
+
+template <typename real>
+void CpReduced<real>::residual(const real *rX, const real *Y, real *R, hipStream_t s) const {
+    k_cpsp_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rowptr.p, colidx.p, rval.p, rX, Y, R);
     PFDR_HIP(hipGetLastError());
 }
 
@@ -325,5 +559,7 @@ void CpCsc<real>::gradient(const real *R, real *DfS, hipStream_t s) const {
 
 template struct CpCsc<float>;
 template struct CpCsc<double>;
+template struct CpReduced<float>;
+template struct CpReduced<double>;
 
 }  // namespace pfdr

@@ -3,16 +3,45 @@
 // the full-size A (pfdr_cp_sparse.hip owns the kernels):
 //   colsum    the component column sums rA (N-by-rV, dense) of pfdr_cp_reduce
 //             and of the drivers' initialize() (one component, Vc = identity)
+//   reduced   the same sums kept sparse: rA as a CSC with its CSR view
+//             (CpReduced), for the direct branch of pfdr_cp_reduce
 //   gradient  DfS = -A^t R, the base of pfdr_cpgraph_gradient for N > 0
 //   take      the copy and the structural checks of a caller's pfdr_csc
-// Both sums add the stored entries only, from +0, in the order the dense
+// Every sum adds the stored entries only, from +0, in the order the dense
 // loops add the whole column or row -- the argument of pfdr_sparse.hpp: the
 // skipped terms are +-0 -- so they give the dense kernels' bytes on the
-// densified matrix, and everything downstream of rA and DfS is the dense code.
+// densified matrix.  Downstream of a dense rA and of DfS runs the dense code;
+// downstream of a CpReduced run its own column norms, scaling and residual,
+// which skip +-0 terms in the same way.
 #pragma once
 #include "pfdr_dev.hpp"
 
 namespace pfdr {
+
+// The reduced operator rA (N-by-rV) on the device: a CSC (columns =
+// components, rows strictly ascending inside a column) and its CSR view (the
+// columns of a row ascending).  A pair (n, rv) is stored iff A stores some
+// entry A[n, v] with v in component rv, whatever the sum comes to.
+template <typename real>
+struct CpReduced {
+    int N = 0, rV = 0;
+    int64_t rnnz = 0;
+    DevBuf<int64_t> colptr, rowptr;  // rV + 1, N + 1
+    DevBuf<int> rowidx, ecol;        // CSC: the row / the column of stored entry j
+    DevBuf<int> colidx;              // CSR: the column of stored entry h
+    DevBuf<real> val, rval;          // CSC / CSR values
+
+    // l[rv] = sqrt of the squares of column rv's values added in ascending row
+    // order from +0 (k_cp_colnorm's order).  Returns the first rv whose l is 0
+    // or not finite, or -1.
+    long colnorm(real *l, hipStream_t s) const;
+    // every value /= (mul: *=) l[its column], in both views
+    void scale(const real *l, int mul, hipStream_t s);
+    // R[n] = Y[n] - (sum of rval * rX[colidx] over row n's entries, rv
+    // ascending, from +0): k_cpq_residual's bytes on the densified rA
+    void residual(const real *rX, const real *Y, real *R, hipStream_t s) const;
+    pfdr_csc csc() const { return pfdr_csc{rnnz, colptr.p, rowidx.p, val.p}; }
+};
 
 // The checks of a pfdr_csc that need no device (NULL arrays, nnz): the
 // offence, or nullptr.
@@ -34,14 +63,24 @@ struct CpCsc {
     // nullptr: one component, Vc = nullptr: the identity.  The scratch (a sort
     // of nnz pairs) is allocated by the first call and kept.
     void colsum(int rV, const int *rVc, const int *Vc, real *rA, hipStream_t s);
+    // The same sums as a CpReduced: the heads of the (row, component) runs, in
+    // the sorted order, are its CSR; a stable sort of them by component gives
+    // its CSC.  Every value is its run's sequential sum, the byte pattern of
+    // colsum's element.  Synchronises once (rnnz comes back); scratch as colsum.
+    void reduced(int rV, const int *rVc, const int *Vc, CpReduced<real> &out, hipStream_t s);
     // DfS[v] = -(sum of val[e] R[rowidx[e]] over column v's entries in stored order)
     void gradient(const real *R, real *DfS, hipStream_t s) const;
 
   private:
+    // entries sorted by row, stably, from the Vc-order numbering: ko = rows,
+    // sc = components, sv = values
+    void sort_entries(int rV, const int *rVc, const int *Vc, hipStream_t s);
     DevBuf<int64_t> off, sums;  // the entries before position i of Vc
     DevBuf<int> cv, sc;         // component of a vertex / of a sorted entry
     DevBuf<real> sv;            // value of a sorted entry
     DevBuf<unsigned> ki, ko, vi, vo;
+    DevBuf<int64_t> pos, psums;  // reduced(): the run heads before sorted entry p
+    DevBuf<unsigned> hrow;       // reduced(): the row of head h
 };
 
 // pfdr_cp_reduce_* (pfdr_cp.hip) with the column sums taken from A; every
@@ -49,6 +88,18 @@ struct CpCsc {
 template <typename real>
 int cp_reduce_sparse(CpCsc<real> &A, const real *Y, int rV, const int *rVc, const int *Vc,
                      int preAt, real *rA, real *rAA, real *rY, real *L);
+
+// The direct branch (preAt = 0) of pfdr_cp_reduce_* on the stored entries
+// (pfdr_cp.hip): rA as a CpReduced, l = its column norms (device, rV), and
+// L = l (l c) (device, rV) with c the squared norm of rA with every column
+// divided by its l, by the CSC power method of pfdr_operator_norm_csc_*; the
+// values go through the reference's divide-then-multiply round trip.  Returns
+// -1, or the first column whose l is 0 or not finite: rA is then as summed
+// and L is not written (a sparse session refuses such a column).
+template <typename real>
+long cp_reduce_sparse_direct(CpCsc<real> &A, int rV, const int *rVc, const int *Vc, real normTol,
+                             int normItMax, int normNbInit, CpReduced<real> &rA, real *l, real *L,
+                             hipStream_t s);
 
 // pfdr_cpgraph_gradient (pfdr_cpgraph.hip) for N > 0 with the base taken from
 // A, a CpCsc of the graph's real type; R on the device, DfS stays there.

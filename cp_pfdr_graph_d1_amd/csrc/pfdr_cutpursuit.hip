@@ -303,7 +303,22 @@ struct QuadDriver : CpDriverBase {
     // k_cpq_residual, as the loop does
     void residual_from_state() {
         CP_ABI(pfdr_cpgraph_get_components(g, nullptr, nullptr, dVc.p, drVc.p, PFDR_MEM_DEVICE));
-        DevBuf<real> rA((size_t)N * rV), L(rV);
+        DevBuf<real> L(rV);
+        if (reduced == PFDR_REDUCED_SPARSE) {
+            // the same sums over the stored entries, through the equilibration's
+            // divide and multiply (no norm: R does not read L); a column of
+            // norm 0 takes the dense branch, as in the loop
+            CpReduced<real> rs;
+            sp.reduced(rV, drVc.p, dVc.p, rs, s);
+            if (rs.colnorm(L.p, s) < 0) {
+                rs.scale(L.p, 0, s);
+                rs.scale(L.p, 1, s);
+                rs.residual(drX.p, dY.p, dR.p, s);
+                PFDR_HIP(hipStreamSynchronize(s));
+                return;
+            }
+        }
+        DevBuf<real> rA((size_t)N * rV);
         reduce(0, rA.p, nullptr, nullptr, L.p);
         k_cpq_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rV, rA.p, drX.p, dY.p, dR.p);
         PFDR_HIP(hipGetLastError());
@@ -327,6 +342,7 @@ struct QuadDriver : CpDriverBase {
         }
         obj_known = false;
     }
+    bool holds_sparse_A() const override { return sp.nnz > 0; }
     const void *values() const override { return drX.p; }
     const void *residual() const override { return N > 0 ? dR.p : nullptr; }
     void forget_objective() override { obj_known = false; }
@@ -341,6 +357,7 @@ struct QuadDriver : CpDriverBase {
         real *Obj = (real *)Obj_, *Dif = (real *)Dif_;
         auto t = t0;
         st = CpStats{};
+        sparse_its = dense_direct_its = max_rnnz = 0;
         const bool bounds = flavour == Flavour::Bounds;
         // flavour: the two-layer cut (duplex :469-545); else one cut when nothing
         // but the d1 term bends the functional (bounds :392), or two
@@ -454,12 +471,30 @@ struct QuadDriver : CpDriverBase {
             // l1 :671 / bounds :648
             const int preAt = N <= 0 || rV < (2L * N * pit) / ((long)N + pit);
             DevBuf<real> rA, rAAd, rYd, L(rV);
-            if (N > 0) rA.alloc((size_t)N * rV);
-            if (preAt) {
-                rYd.alloc(rV);
-                rAAd.alloc(N == 0 ? (size_t)rV : (size_t)rV * rV);
+            // a direct iteration of the sparse mode keeps rA sparse, unless a
+            // reduced column has norm 0 (a sparse session refuses it): then,
+            // and in every other case, the dense rA
+            CpReduced<real> rs;
+            bool sparse_rA = false;
+            if (!preAt && reduced == PFDR_REDUCED_SPARSE) {
+                DevBuf<real> l(rV);
+                sparse_rA = cp_reduce_sparse_direct<real>(sp, rV, drVc.p, dVc.p, real(1e-3), 100,
+                                                          10, rs, l.p, L.p, s) < 0;
             }
-            reduce(preAt, rA.p, rAAd.p, rYd.p, L.p);
+            if (!sparse_rA) {
+                if (N > 0) rA.alloc((size_t)N * rV);
+                if (preAt) {
+                    rYd.alloc(rV);
+                    rAAd.alloc(N == 0 ? (size_t)rV : (size_t)rV * rV);
+                }
+                reduce(preAt, rA.p, rAAd.p, rYd.p, L.p);
+            }
+            if (sparse_rA) {
+                sparse_its++;
+                if (rs.rnnz > max_rnnz) max_rnnz = rs.rnnz;
+            } else if (!preAt) {
+                dense_direct_its++;
+            }
             st.graph += since(t);
             // PFDR from zero (l1 :843-859 / bounds :824-836)
             t = clock::now();
@@ -476,7 +511,7 @@ struct QuadDriver : CpDriverBase {
                 p.N = preAt ? (N == 0 ? 0 : -rV) : N;
                 p.X = drX.p;
                 p.Y = preAt ? rYd.p : dY.p;
-                p.A = preAt ? rAAd.p : rA.p;
+                p.A = preAt ? rAAd.p : sparse_rA ? nullptr : rA.p;
                 p.Eu = rEu.p;
                 p.Ev = rEv.p;
                 p.La_d1 = rLa.p;
@@ -492,7 +527,8 @@ struct QuadDriver : CpDriverBase {
                 p.difTol = (real)q.difTol;
                 p.itMax = q.itMax;
                 p.verbose = verbose;
-                pit = cp_pfdr_solve(p, sizeof(real) * rV, s);
+                if (sparse_rA) pit = cp_pfdr_solve_sparse(p, rs.csc(), sizeof(real) * rV, s);
+                else pit = cp_pfdr_solve(p, sizeof(real) * rV, s);
             }
             st.pfdr += since(t);
             st.pfdr_it += pit;
@@ -502,7 +538,9 @@ struct QuadDriver : CpDriverBase {
             st.graph += since(t);
             // progress (l1 :888-923 / bounds :865-901)
             t = clock::now();
-            if (N > 0) {
+            if (sparse_rA) {
+                rs.residual(drX.p, dY.p, dR.p, s);
+            } else if (N > 0) {
                 k_cpq_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rV, rA.p, drX.p, dY.p, dR.p);
                 PFDR_HIP(hipGetLastError());
             }

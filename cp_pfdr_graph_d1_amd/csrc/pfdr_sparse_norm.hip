@@ -210,6 +210,10 @@ const char *csc_entry_args(int N, int V, const pfdr_csc *A, int mem) {
     return cp_csc_args(A);
 }
 
+}  // namespace
+
+// pfdr_sparse_view.hpp: the entries' power method, also cut pursuit's on its
+// sparse reduced operator
 template <typename real>
 real operator_norm_sparse(const SparseView<real> &A, real nTol, int itMax, int nbInit, int verbose,
                           hipStream_t s) {
@@ -263,6 +267,12 @@ real operator_norm_sparse(const SparseView<real> &A, real nTol, int itMax, int n
     if (verbose) { printf("done.\n"); fflush(stdout); }
     return best;
 }
+template float operator_norm_sparse<float>(const SparseView<float> &, float, int, int, int,
+                                           hipStream_t);
+template double operator_norm_sparse<double>(const SparseView<double> &, double, int, int, int,
+                                             hipStream_t);
+
+namespace {
 
 template <typename real>
 int opnorm_csc_host(const char *fn, int N, int V, const pfdr_csc *A, int mem, real nTol, int itMax,

@@ -33,4 +33,11 @@ template <typename real>
 std::shared_ptr<void> sparse_view(int N, int V, const pfdr_csc *A, int mem, hipStream_t s,
                                   SparseView<real> &out);
 
+// ||A||^2 by the power method of pfdr_operator_norm_csc_* (pfdr_sparse_norm.hip)
+// on a view whose arrays are already on the device; it reads N, V and the six
+// arrays only.  nbInit starts, the best one returned.
+template <typename real>
+real operator_norm_sparse(const SparseView<real> &A, real nTol, int itMax, int nbInit, int verbose,
+                          hipStream_t s);
+
 }  // namespace pfdr

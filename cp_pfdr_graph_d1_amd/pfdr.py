@@ -26,6 +26,7 @@ PFDR_F32, PFDR_F64 = 0, 1
 PFDR_MEM_HOST, PFDR_MEM_DEVICE = 0, 1
 PFDR_KIND_L1, PFDR_KIND_BOUNDS, PFDR_KIND_SIMPLEX = 0, 1, 2
 SCAL, DIAG = 0, 1
+PFDR_REDUCED_DENSE, PFDR_REDUCED_SPARSE = 0, 1
 REORDER_AUTO, REORDER_ON, REORDER_OFF = 0, 1, 2
 # iterate-evolution statistic (include/pfdr_mi355x.h PFDR_EVOLUTION_*)
 EVOLUTION_AUTO, EVOLUTION_SEQUENTIAL, EVOLUTION_TREE = 0, 1, 2
@@ -50,6 +51,7 @@ EXPORTED = (
     "pfdr_radix_sort_pairs_u32", "pfdr_radix_sort_pairs_u64",
     "pfdr_cp_reduce_f32", "pfdr_cp_reduce_f64",
     "pfdr_cp_reduce_csc_f32", "pfdr_cp_reduce_csc_f64",
+    "pfdr_cp_reduce_csc_sparse_f32", "pfdr_cp_reduce_csc_sparse_f64",
     "pfdr_cpgraph_create", "pfdr_cpgraph_destroy", "pfdr_cpgraph_set_active",
     "pfdr_cpgraph_get_active", "pfdr_cpgraph_set_components", "pfdr_cpgraph_get_components",
     "pfdr_cpgraph_set_values", "pfdr_cpgraph_components", "pfdr_cpgraph_reduced_graph",
@@ -73,6 +75,7 @@ EXPORTED = (
     "pfdr_cp_solver_run",
     "pfdr_cp_solver_get_state", "pfdr_cp_solver_set_state", "pfdr_cp_solver_set_partition",
     "pfdr_cp_solver_set_penalties", "pfdr_cp_solver_stats",
+    "pfdr_cp_solver_set_reduced", "pfdr_cp_solver_reduced_stats",
     "pfdr_cpgraph_set_weights", "pfdr_cpgraph_set_active_by_labels",
     "pfdr_session_create", "pfdr_session_run", "pfdr_session_prepare", "pfdr_session_result",
     "pfdr_session_device_x", "pfdr_session_set_profiling", "pfdr_session_profile_filter",
@@ -181,6 +184,9 @@ def _solver_argtypes(lib, vp):
     lib.pfdr_cp_solver_set_partition.argtypes = [vp, C.c_int, vp, vp, C.c_int]
     lib.pfdr_cp_solver_set_penalties.argtypes = [vp, vp, vp, C.c_int]
     lib.pfdr_cp_solver_stats.argtypes = [vp, vp, vp, vp]
+    if hasattr(lib, "pfdr_cp_solver_set_reduced"):
+        lib.pfdr_cp_solver_set_reduced.argtypes = [vp, C.c_int]
+        lib.pfdr_cp_solver_reduced_stats.argtypes = [vp, vp, vp, vp]
 
 
 def load():
@@ -567,6 +573,18 @@ class Lib:
         _check(self.lib.pfdr_cp_solver_stats(handle, seconds, counts, setup_seconds),
                "pfdr_cp_solver_stats")
 
+    def cp_solver_set_reduced(self, handle, mode):
+        _check(self.lib.pfdr_cp_solver_set_reduced(handle, int(mode)),
+               "pfdr_cp_solver_set_reduced")
+
+    def cp_solver_reduced_stats(self, handle):
+        """-> (sparse iterations, dense direct iterations, max rnnz) of the last run"""
+        out = np.zeros(3, np.int64)
+        a = out.ctypes.data
+        _check(self.lib.pfdr_cp_solver_reduced_stats(handle, a, a + 8, a + 16),
+               "pfdr_cp_solver_reduced_stats")
+        return tuple(int(x) for x in out)
+
     def cp_loss_d1_simplex_stats(self, n_exp=64):
         """pfdr_cp_loss_d1_simplex_stats of this thread's last cp_loss_d1_simplex
         -> dict: seconds per phase, counts, rounds / relabels per expansion"""
@@ -799,15 +817,15 @@ def CP_PFDR_graph_loss_d1_simplex(Q, al, Eu, Ev, La_d1, CP_difTol, CP_itMax, PFD
 
 
 def _cp_sparse_run(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho, condMin,
-                   difRcd, difTol, itMax, verbose):
+                   difRcd, difTol, itMax, verbose, reduced="dense"):
     """Lib._cp_quadratic for a CSC A: one CPSolver, one run (the solver's first
-    run is defined to equal the one-call entry)"""
+    run is defined to equal the one-call entry); ``reduced``: CPSolver's"""
     if flavour == "bounds":
         kw = dict(lo=own[0], hi=own[1])
     else:
         kw = dict(La_l1=own[0], positivity=own[1], duplex=flavour == "duplex")
     s = CPSolver("bounds" if flavour == "bounds" else "l1", Y, Eu, Ev, La_d1,
-                 A=A.astype(Y.dtype), N=N, **kw)
+                 A=A.astype(Y.dtype), N=N, reduced=reduced, **kw)
     try:
         return s.run(CP_difTol, CP_itMax, rho, condMin, difRcd, difTol, itMax, verbose)
     finally:
@@ -815,17 +833,21 @@ def _cp_sparse_run(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax,
 
 
 def _cp_front(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho, condMin, difRcd,
-              difTol, itMax, verbose, time, obj, dif):
+              difTol, itMax, verbose, time, obj, dif, reduced="dense"):
     """the bounds ("bounds", own = Bnd) and duplex ("duplex", own = (La_l1,
     positivity)) front-ends' common call -> (Cv, rX, CP_it, Time, Obj, Dif), the
     records not asked for None"""
     Eu, Ev = _edges(Eu, Ev)
     if flavour == "duplex":
         own = (_scal_or_vec(own[0], V, Y.dtype), own[1])
-    call = _cp_sparse_run if isinstance(A, CSC) else Lib()._cp_quadratic
+    call, kw = Lib()._cp_quadratic, {}
+    if isinstance(A, CSC):
+        call, kw = _cp_sparse_run, dict(reduced=reduced)
+    elif _reduced_mode(reduced) != PFDR_REDUCED_DENSE:
+        raise ValueError('reduced="sparse" needs A as a CSC')
     Cv, rX, it, Obj, Dif, Time = call(
         flavour, V, N, Y, A, Eu, Ev, np.asarray(La_d1, Y.dtype), own, CP_difTol, CP_itMax, rho,
-        condMin, difRcd, difTol, itMax, verbose)
+        condMin, difRcd, difTol, itMax, verbose, **kw)
     return Cv, rX, it, Time if time else None, Obj if obj else None, Dif if dif else None
 
 
@@ -840,19 +862,21 @@ def _cp_matrix(A, dt):
 
 def CP_PFDR_graph_quadratic_d1_bounds(Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax, PFDR_rho,
                                       PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
-                                      verbose=0, time=False, obj=False, dif=False):
+                                      verbose=0, time=False, obj=False, dif=False,
+                                      reduced="dense"):
     """octave/mex/CP_PFDR_graph_quadratic_d1_bounds_mex.cpp: cut pursuit for
     1/2 ||y - A x||^2 + sum_e La_d1 |x_u - x_v| over Bnd[0] <= x <= Bnd[1]
     (+-inf: no bound), A N-by-V (an array, or a CSC: the same bytes as its
     densified matrix gives), the whole loop on the GPU
     (pfdr_cp_quadratic_d1_bounds).  Returns (Cv, rX, CP_it, Time, Obj, Dif): the
     component of every vertex (int32[V]), the value of every component -- the
-    minimiser is rX[Cv] -- and the records asked for (None otherwise)."""
+    minimiser is rX[Cv] -- and the records asked for (None otherwise).
+    reduced="sparse" (a CSC A only): CPSolver's sparse reduced operator."""
     dt = np.result_type(Y, np.float32)
     A, (N, V) = _cp_matrix(A, dt)
     return _cp_front("bounds", V, N, np.asarray(Y, dt).ravel(), A, Eu, Ev, La_d1, Bnd, CP_difTol,
                      CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol, PFDR_itMax,
-                     verbose, time, obj, dif)
+                     verbose, time, obj, dif, reduced)
 
 
 def CP_PFDR_graph_quadratic_d1_bounds_AtA(AtY, AtA, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMax,
@@ -886,19 +910,20 @@ def CP_PFDR_graph_l22_d1_bounds(Y, La_l2, Eu, Ev, La_d1, Bnd, CP_difTol, CP_itMa
 def CP_PFDR_graph_quadratic_d1_l1_duplex(Y, A, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
                                          CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd,
                                          PFDR_difTol, PFDR_itMax, verbose=0, time=False,
-                                         obj=False, dif=False):
+                                         obj=False, dif=False, reduced="dense"):
     """octave/mex/CP_PFDR_graph_quadratic_d1_l1_duplex_mex.cpp: cut pursuit for
     1/2 ||y - A x||^2 + sum_e La_d1 |x_u - x_v| + sum_v La_l1 |x_v| (x >= 0 with
     positivity), A N-by-V (an array or a CSC), one two-layer cut per iteration,
     the whole loop on the GPU (pfdr_cp_quadratic_d1_l1_duplex).  La_l1: array,
     scalar or None.  Returns (Cv, rX, CP_it, Time, Obj, Dif): the component of every vertex
     (int32[V]), the value of every component -- the minimiser is rX[Cv] -- and
-    the records asked for (None otherwise)."""
+    the records asked for (None otherwise).  reduced="sparse" (a CSC A only):
+    CPSolver's sparse reduced operator."""
     dt = np.result_type(Y, np.float32)
     A, (N, V) = _cp_matrix(A, dt)
     return _cp_front("duplex", V, N, np.asarray(Y, dt).ravel(), A, Eu, Ev, La_d1,
                      (La_l1, positivity), CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin,
-                     PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif)
+                     PFDR_difRcd, PFDR_difTol, PFDR_itMax, verbose, time, obj, dif, reduced)
 
 
 def CP_PFDR_graph_l22_d1_l1_duplex(Y, La_l2, Eu, Ev, La_d1, La_l1, positivity, CP_difTol,
@@ -1016,14 +1041,18 @@ def PFDR_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity
     return X, it
 
 
-def _cp_binding(flavour, obs, source, target, edge_weight, A, l1_weight, positivity, *args):
+def _cp_binding(flavour, reduced, obs, source, target, edge_weight, A, l1_weight, positivity,
+                *args):
     """CP_quadratic_l1 and CP_quadratic_l1_duplex after their defaults; ``args``:
     Lib._cp_quadratic's from CP_difTol on"""
     dt, N, V, mode, A, obs, Eu, Ev, ew, lw = _binding_inputs(obs, source, target, edge_weight,
                                                              A, l1_weight)
     if mode == "sparse":
-        r = _cp_sparse_run(flavour, V, N, obs.ravel(), A, Eu, Ev, ew, (lw, positivity), *args)
+        r = _cp_sparse_run(flavour, V, N, obs.ravel(), A, Eu, Ev, ew, (lw, positivity), *args,
+                           reduced=reduced)
         return r[0].astype(np.uint32), r[1]
+    if _reduced_mode(reduced) != PFDR_REDUCED_DENSE:
+        raise ValueError('reduced="sparse" needs A as a CSC')
     if mode == "identity":
         N, A = 0, None
     elif mode == "diagonal":
@@ -1036,26 +1065,29 @@ def _cp_binding(flavour, obs, source, target, edge_weight, A, l1_weight, positiv
 
 def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0,
                     PFDR_rho=1.0, PFDR_condMin=1e-3, CP_difTol=1e-3, PFDR_difRcd=0.0,
-                    PFDR_difTol=1e-4, CP_itMax=10, PFDR_itMax=10000, verbose=0):
+                    PFDR_difTol=1e-4, CP_itMax=10, PFDR_itMax=10000, verbose=0, reduced="dense"):
     """The reference's Python binding (python/CP_quadratic_l1_py.cpp:68-76,
     188-259): cut pursuit for F(x) = 1/2 ||A x - obs||^2 + sum_e edge_weight
     |x_u - x_v| + sum_v l1_weight |x_v|, same signature, defaults and input
     conventions (those of PFDR_quadratic_l1; a CSC A runs the resumable solver
     once and gives the bytes of its densified matrix), the whole loop on the GPU
     (pfdr_cp_quadratic_d1_l1).  Returns (Cv, rX): the component of every
-    vertex (uint32, as the binding) and the value of every component."""
-    return _cp_binding("l1", obs, source, target, edge_weight, A, l1_weight, positivity,
+    vertex (uint32, as the binding) and the value of every component.
+    reduced="sparse" (a CSC A only): CPSolver's sparse reduced operator, which
+    agrees with the default to the solvers' tolerances, not to the byte."""
+    return _cp_binding("l1", reduced, obs, source, target, edge_weight, A, l1_weight, positivity,
                        CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
                        PFDR_itMax, verbose)
 
 
 def CP_quadratic_l1_duplex(obs, source, target, edge_weight, A, l1_weight, positivity=0,
                            PFDR_rho=1.0, PFDR_condMin=1e-3, CP_difTol=1e-3, PFDR_difRcd=0.0,
-                           PFDR_difTol=1e-4, CP_itMax=10, PFDR_itMax=10000, verbose=0):
+                           PFDR_difTol=1e-4, CP_itMax=10, PFDR_itMax=10000, verbose=0,
+                           reduced="dense"):
     """CP_quadratic_l1 through the duplex driver (one two-layer cut per
     iteration, pfdr_cp_quadratic_d1_l1_duplex): same signature, defaults, input
     conventions and returns."""
-    return _cp_binding("duplex", obs, source, target, edge_weight, A, l1_weight, positivity,
+    return _cp_binding("duplex", reduced, obs, source, target, edge_weight, A, l1_weight, positivity,
                        CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
                        PFDR_itMax, verbose)
 
@@ -1443,13 +1475,26 @@ def lipschitz_diag(csc):
     return L, csc.dtype.type(bound.value)
 
 
+def _reduced_mode(reduced):
+    """"dense" / "sparse" -> PFDR_REDUCED_*; an integer as it is (the library
+    refuses the ones it does not know)"""
+    modes = {"dense": PFDR_REDUCED_DENSE, "sparse": PFDR_REDUCED_SPARSE}
+    if isinstance(reduced, str):
+        if reduced not in modes:
+            raise ValueError('reduced must be "dense" or "sparse", got %r' % (reduced,))
+        return modes[reduced]
+    return int(reduced)
+
+
 def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normItMax=100,
-              normNbInit=10):
+              normNbInit=10, reduced="dense"):
     """CP reduced-problem builder (pfdr_cp_reduce_*): A is (N, V) for
     N > 0 (or (V, V) A^tA for N < 0, length-V diagonal / None for N = 0),
     comp_ptr (rV + 1) and comp_vertices (V) the components; a CSC A (N > 0)
     goes through pfdr_cp_reduce_csc_* and gives the bytes of its densified
-    matrix.  Returns dict rA, rAA, rY, L, Leq (None where not formed)."""
+    matrix.  Returns dict rA, rAA, rY, L, Leq (None where not formed).
+    reduced="sparse" (a CSC A, preAt=False): pfdr_cp_reduce_csc_sparse_*, "rA"
+    is a host CSC (N-by-rV) that is never densified, rAA and rY are None."""
     Y = np.asarray(Y)
     dt = Y.dtype
     ct, sfx, _ = _real(dt)
@@ -1458,6 +1503,29 @@ def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normIt
     rV, V = ptr.size - 1, Vc.size
     Af = None
     sparse = isinstance(A, CSC)
+    mode = _reduced_mode(reduced)
+    if mode not in (PFDR_REDUCED_DENSE, PFDR_REDUCED_SPARSE):
+        raise ValueError('cp_reduce: reduced must be "dense" or "sparse", got %r' % (reduced,))
+    if mode == PFDR_REDUCED_SPARSE:
+        if not sparse:
+            raise ValueError('cp_reduce: reduced="sparse" needs A as a CSC')
+        if preAt:
+            raise ValueError('cp_reduce: reduced="sparse" is the direct branch, preAt=False')
+        A = A.to_host().astype(dt)
+        csc = A.struct()
+        Yc = np.ascontiguousarray(Y)
+        rnnz = C.c_int64(0)
+        rcolptr = np.zeros(rV + 1, np.int64)
+        rrowidx, rval = np.zeros(A.nnz, np.int32), np.zeros(A.nnz, dt)
+        L, Leq = np.zeros(rV, dt), np.zeros(rV, dt)
+        p = lambda a: C.c_void_p(a.ctypes.data)
+        _check(getattr(load(), "pfdr_cp_reduce_csc_sparse_" + sfx)(
+            C.c_int(N), C.c_int(V), C.byref(csc), p(Yc), C.c_int(rV), p(ptr), p(Vc),
+            PFDR_MEM_HOST, ct(normTol), C.c_int(normItMax), C.c_int(normNbInit), C.byref(rnnz),
+            p(rcolptr), p(rrowidx), p(rval), p(L), p(Leq)), "pfdr_cp_reduce_csc_sparse")
+        n = rnnz.value
+        return {"rA": CSC(rcolptr, rrowidx[:n].copy(), rval[:n].copy(), N), "rAA": None,
+                "rY": None, "L": L, "Leq": Leq}
     if sparse:
         A = A.to_host().astype(dt)
         csc = A.struct()
@@ -1742,7 +1810,24 @@ class CPGraph:
             pass
 
 
-class CPSolver:
+class _CPSolverType(type):
+    """CPSolver(..., reduced="dense" | "sparse"): the keyword is no argument of
+    the constructor proper but a set_reduced() on the finished solver, which
+    the library refuses (PFDRError) unless A came as a CSC"""
+
+    def __call__(cls, *args, reduced="dense", **kw):
+        mode = _reduced_mode(reduced)
+        s = super().__call__(*args, **kw)
+        if mode != PFDR_REDUCED_DENSE:
+            try:
+                s.set_reduced(mode)
+            except Exception:
+                s.close()
+                raise
+        return s
+
+
+class CPSolver(metaclass=_CPSolverType):
     """The resumable cut pursuit (pfdr_cp_solver_*): the problem, its graph and
     the cut-pursuit state stay on the device between calls.
 
@@ -1753,7 +1838,11 @@ class CPSolver:
     is borrowed and kept alive here).  A may be a CSC ("l1" and "bounds", N > 0
     or taken from it; host, or to_device() with the other arrays on the GPU):
     it is copied, V is its column count, and every call gives the bytes of the
-    solver on the densified matrix (pfdr_cp_solver_create_sparse).  The first run() equals the matching
+    solver on the densified matrix (pfdr_cp_solver_create_sparse).  With a CSC,
+    reduced="sparse" (or set_reduced) keeps the reduced operator of a direct
+    iteration sparse as well (pfdr_cp_solver_set_reduced): the dense N-by-rV
+    array is never allocated there, and a run then agrees with the default to the
+    solvers' tolerances.  The first run() equals the matching
     Lib.cp_* call byte for byte; every later one is the reference's warm restart
     from the state the handle holds."""
 
@@ -1914,6 +2003,17 @@ class CPSolver:
         La_d1, La_l1 = cvt(La_d1), cvt(La_l1)
         self._L.cp_solver_set_penalties(self._h, self._addr(La_d1), self._addr(La_l1),
                                         PFDR_MEM_DEVICE if dev else PFDR_MEM_HOST)
+
+    def set_reduced(self, reduced):
+        """"dense" or "sparse" (pfdr_cp_solver_set_reduced): how the reduced
+        operator of a direct iteration is kept; a solver with a CSC A only.
+        The state is kept."""
+        self._L.cp_solver_set_reduced(self._h, _reduced_mode(reduced))
+
+    def reduced_stats(self):
+        """-> (iterations solved on a sparse rA, direct iterations solved on a
+        dense one, the most entries a sparse rA held) of the last run"""
+        return self._L.cp_solver_reduced_stats(self._h)
 
     def stats(self):
         """-> dict: seconds per phase and counts of the last run, and the seconds

@@ -507,6 +507,37 @@ int pfdr_cp_reduce_csc_f64(int N, int V, const pfdr_csc *A, const double *Y, int
                            const int *rVc, const int *Vc, int preAt, int mem, double normTol,
                            int normItMax, int normNbInit, double *rA, double *rAA, double *rY,
                            double *L, double *Leq);
+/* pfdr_cp_reduce_csc_* at preAt = 0 with the reduced operator rA returned as
+ * a CSC and never densified: *rnnz entries (host scalar), rcolptr[rV + 1],
+ * rrowidx and rval (capacity A->nnz each; host or device per mem, allocated
+ * by the caller), columns = components, rows strictly ascending inside a
+ * column.  A pair (n, rv) is stored iff A stores some entry A[n, v] with v in
+ * component rv, whatever the sum comes to (a sum that cancels is a stored
+ * zero), so *rnnz <= A->nnz and the structure depends on A's structure and the
+ * partition only.  Every value is the sum of the stored entries A[n, Vc[i]]
+ * over the component's range of Vc, i ascending, from +0: the bytes of the
+ * dense rA's element, also after the equilibration's divide-and-multiply
+ * round trip, which the values go through element by element.  Leq = l, the
+ * column norms over the stored entries in ascending row order, has the dense
+ * entry's bytes as well.  L = l (l c), where c is the squared norm of rA with
+ * every column divided by its l, by the power method of
+ * pfdr_operator_norm_csc_* on those entries (normTol, normItMax, normNbInit
+ * as passed); the dense entry's c comes from its own power method, so the two
+ * L agree to the power methods' tolerance, not to the bit.  A reduced column
+ * of norm 0 (or not finite) is PFDR_ERR_ARG naming rv: a sparse session
+ * refuses such a column.  The argument checks are pfdr_cp_reduce_csc_*'s, and
+ * rnnz, rcolptr, rrowidx and rval are required.  No floating atomics: the same
+ * bytes on every run. */
+int pfdr_cp_reduce_csc_sparse_f32(int N, int V, const pfdr_csc *A, const float *Y, int rV,
+                                  const int *rVc, const int *Vc, int mem, float normTol,
+                                  int normItMax, int normNbInit, int64_t *rnnz,
+                                  int64_t *rcolptr, int32_t *rrowidx, float *rval, float *L,
+                                  float *Leq);
+int pfdr_cp_reduce_csc_sparse_f64(int N, int V, const pfdr_csc *A, const double *Y, int rV,
+                                  const int *rVc, const int *Vc, int mem, double normTol,
+                                  int normItMax, int normNbInit, int64_t *rnnz,
+                                  int64_t *rcolptr, int32_t *rrowidx, double *rval, double *L,
+                                  double *Leq);
 
 /* ------------------------------------------- cut-pursuit graph steps -- */
 /* The full-graph work of every cut-pursuit iteration around the reduced
@@ -849,7 +880,8 @@ int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem *p);
  * pursuit reads the full-size A in three places -- initialize()'s column sum,
  * pfdr_cp_reduce's component column sums and the gradient -A^t R -- and those
  * walk the stored entries in the dense loops' order; the reduced matrix stays
- * dense (p->N * rV reals) and the rest of the loop is the dense solver's code.
+ * dense (p->N * rV reals; pfdr_cp_solver_set_reduced below keeps it sparse
+ * instead) and the rest of the loop is the dense solver's code.
  * Every run, state and statistic therefore equals, byte for byte, those of
  * pfdr_cp_solver_create on the densified matrix, and every other
  * pfdr_cp_solver_* call works on the handle unchanged.  PFDR_ERR_ARG before
@@ -860,6 +892,33 @@ int pfdr_cp_solver_create(pfdr_cp_solver **out, const pfdr_cp_problem *p);
  * handle is created. */
 int pfdr_cp_solver_create_sparse(pfdr_cp_solver **out, const pfdr_cp_problem *p,
                                  const pfdr_csc *A);
+/* How a solver created by pfdr_cp_solver_create_sparse keeps the reduced
+ * operator rA of an iteration that works on rA directly (the reference's
+ * branch without premultiplication, taken when rV >= 2 N pit / (N + pit), pit
+ * the previous PFDR iteration count).  PFDR_REDUCED_DENSE, the default: N * rV
+ * reals, every byte as documented above.  PFDR_REDUCED_SPARSE: rA is the CSC
+ * of pfdr_cp_reduce_csc_sparse_* with its CSR view, built on the device; the
+ * N * rV array is never allocated, PFDR runs as a sparse session on it
+ * (pfdr_session_create_sparse, device arrays) and the residual walks its
+ * rows.  rA's values, l and the residual keep the dense mode's bytes; L and
+ * the PFDR iterates follow another power method's estimate of c and another
+ * session, so a run agrees with the dense mode's to the solvers' tolerances
+ * and equals, byte for byte, the same steps composed through the public
+ * entries.  An iteration whose rA has a column of norm 0 (or not finite)
+ * takes the dense branch, and premultiplied iterations are the dense mode's
+ * in either mode.  With R = NULL, pfdr_cp_solver_set_state and
+ * pfdr_cp_solver_set_partition recompute R over the stored entries: the same
+ * bytes.  May be called between runs; the state is kept.  PFDR_ERR_ARG naming
+ * the offence: a solver not created by pfdr_cp_solver_create_sparse, the
+ * simplex kind, an unknown mode. */
+#define PFDR_REDUCED_DENSE 0
+#define PFDR_REDUCED_SPARSE 1
+int pfdr_cp_solver_set_reduced(pfdr_cp_solver *s, int mode);
+/* Of the last run, any may be NULL: the iterations solved on a sparse rA, the
+ * direct iterations solved on a dense one (all of them in the dense mode, the
+ * zero-norm fallbacks in the sparse mode), the most entries a sparse rA held. */
+int pfdr_cp_solver_reduced_stats(pfdr_cp_solver *s, int64_t *sparse_iterations,
+                                 int64_t *dense_direct_iterations, int64_t *max_rnnz);
 void pfdr_cp_solver_destroy(pfdr_cp_solver *s);
 /* Host outputs, any may be NULL: Time[CP_itMax + 1], Obj[CP_itMax + 1],
  * Dif[CP_itMax] of the solver's real type. */

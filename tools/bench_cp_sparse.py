@@ -13,8 +13,20 @@ in one process.  The first run of each is a warm-up (library initialisation,
 allocator cache); --reps further runs of each are reported, every run on a
 fresh solver.  Prints one JSON line.
 
+--reduced dense|sparse (one or both) chooses how the sparse solver keeps the
+reduced operator of a direct iteration (pfdr_cp_solver_set_reduced); with both,
+the two modes alternate like the solvers above.  A direct iteration needs
+rV >= 2 N pit / (N + pit), about twice the previous PFDR iteration count, so
+--pfdr-itmax must be small for a run to take one: the line reports, per mode,
+how many iterations were solved on a sparse rA and how many direct ones on a
+dense rA (pfdr_cp_solver_reduced_stats), the most entries a sparse rA held
+beside N rV of the final partition, and the device memory in use after the
+mode's runs (hipMemGetInfo through torch; the library's allocator cache keeps
+what a run freed, so run one mode per process for that figure).
+
     python tools/bench_cp_sparse.py --shape 128 128 --kind l1 [--dense] [--dtype f32]
                                     [--CP_itMax 10] [--reps 3]
+                                    [--reduced dense sparse] [--pfdr-itmax 2000]
 """
 import argparse
 import json
@@ -41,7 +53,9 @@ def main():
     ap.add_argument("--CP_difTol", type=float, default=1e-4)
     ap.add_argument("--CP_itMax", type=int, default=10)
     ap.add_argument("--PFDR_difTol", type=float, default=1e-5)
-    ap.add_argument("--PFDR_itMax", type=int, default=2000)
+    ap.add_argument("--PFDR_itMax", "--pfdr-itmax", dest="PFDR_itMax", type=int, default=2000)
+    ap.add_argument("--reduced", nargs="+", choices=["dense", "sparse"], default=["dense"],
+                    help="the sparse solver's reduced operator: one mode, or both alternating")
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     from cp_pfdr_graph_d1_amd import pfdr
@@ -67,38 +81,62 @@ def main():
     run = dict(CP_difTol=args.CP_difTol, CP_itMax=args.CP_itMax, rho=1.5, condMin=1e-3,
                difRcd=0.0, difTol=args.PFDR_difTol, itMax=args.PFDR_itMax)
 
-    def once(A):
+    def device_mb():
+        try:
+            import torch
+            free, total = torch.cuda.mem_get_info()
+            return round((total - free) / 2 ** 20, 1)
+        except Exception:
+            return None
+
+    def once(A, reduced):
         t = time.perf_counter()
         s = pfdr.CPSolver(args.kind, Y, Eu, Ev, La, A=A, N=V, **own)
+        if reduced != "dense":
+            s.set_reduced(reduced)
         r = s.run(**run)
         st = s.stats()
+        if A is csc:
+            st["reduced"] = s.reduced_stats()
         s.close()
         st["wall"] = time.perf_counter() - t
+        st["device_mb"] = device_mb()
         return r, st
 
-    variants = [("sparse", csc)] + ([("dense", dense)] if args.dense else [])
-    runs = {name: [] for name, _ in variants}
+    modes = list(dict.fromkeys(args.reduced))
+    variants = [("sparse" if len(modes) == 1 else "sparse_A_reduced_" + m, csc, m) for m in modes]
+    if args.dense:
+        variants.append(("dense", dense, "dense"))
+    runs = {name: [] for name, _, _ in variants}
     last = {}
     for rep in range(args.reps + 1):
-        for name, A in variants:  # alternating
-            r, st = once(A)
+        for name, A, mode in variants:  # alternating
+            r, st = once(A, mode)
             last[name] = r
             if rep:
                 runs[name].append(st)
     ms = lambda name, key: [round(s[key] * 1e3, 3) for s in runs[name]]
-    r = last["sparse"]
+    first = variants[0][0]
+    r = last[first]
     out = {
         "what": "pfdr_cp_solver_create_sparse + run, one MI355X, host arrays in",
         "problem": "3x3 blur on the %dx%d grid (N = V = %d, nnz = %d), kind %s, %s" % (
             nx, ny, V, csc.nnz, args.kind, args.dtype),
         "CP_it": r[2], "rV": int(r[1].size), "Obj": [float(x) for x in r[3][:r[2] + 1]],
         "phase_ms": {name: dict({k: ms(name, k) for k in PHASES}, wall=ms(name, "wall"))
-                     for name, _ in variants},
-        "pfdr_iterations_total": runs["sparse"][-1]["pfdr_it"],
+                     for name, _, _ in variants},
+        "pfdr_iterations_total": {name: runs[name][-1]["pfdr_it"] for name, _, _ in variants},
+        "PFDR_itMax": args.PFDR_itMax,
+        "reduced": {name: dict(zip(("sparse_iterations", "dense_direct_iterations", "max_rnnz"),
+                                   runs[name][-1]["reduced"]),
+                               N_rV_final=V * int(last[name][1].size),
+                               CP_it=last[name][2], rV=int(last[name][1].size),
+                               device_mb_after=[s["device_mb"] for s in runs[name]])
+                    for name, A, _ in variants if A is csc},
     }
     if args.dense:
         d = last["dense"]
-        out["same_bytes_as_dense"] = bool(
+        out["same_bytes_as_dense"] = len(modes) == 1 and modes[0] == "dense" and bool(
             r[2] == d[2] and all(a.tobytes() == b.tobytes() for a, b in
                                  ((r[0], d[0]), (r[1], d[1]), (r[3], d[3]), (r[4], d[4]))))
     print(json.dumps(out))
