@@ -29,7 +29,6 @@
 #include "pfdr_cp_sparse.hpp"
 #include "pfdr_graph.hpp"
 #include "pfdr_session.hpp"
-#include "pfdr_sparse_view.hpp"
 
 namespace pfdr {
 
@@ -177,6 +176,21 @@ __global__ void k_cp_lipschitz(int rV, const real *__restrict__ l, real c, real 
     L[rv] = x;
 }
 
+// the components on the device: the caller's rVc (rV + 1) and Vc (V), or
+// copies of its host arrays
+struct CpPartition {
+    const int *rVc, *Vc;
+    DevBuf<int> bptr, bVc;
+    CpPartition(int rV, const int *rVc_, int V, const int *Vc_, bool dev, hipStream_t s)
+        : rVc(rVc_), Vc(Vc_) {
+        if (dev) return;
+        upload(bptr, rVc_, (size_t)rV + 1, s);
+        upload(bVc, Vc_, (size_t)V, s);
+        rVc = bptr.p;
+        Vc = bVc.p;
+    }
+};
+
 // sp: the sparse A of N > 0 (A is then unused), already on the device
 template <typename real>
 static int cp_reduce_host(const char *fn, int N, int V, const real *A, const real *Y, int rV,
@@ -201,19 +215,11 @@ static int cp_reduce_host(const char *fn, int N, int V, const real *A, const rea
             return b.p;
         };
         DevBuf<real> bA, bY, brA, brAA, brY, bL, bl;
-        DevBuf<int> bptr, bVc;
         const size_t asz = N > 0 ? (size_t)N * V : N < 0 ? (size_t)V * V : (size_t)V;
         const real *dA = in(bA, A, asz);
         const real *dY = in(bY, Y, N > 0 ? (size_t)N : (size_t)V);
-        const int *dptr = rVc, *dVc = Vc;
-        if (!dev) {
-            bptr.alloc(rV + 1);
-            bVc.alloc(V);
-            PFDR_HIP(hipMemcpyAsync(bptr.p, rVc, (rV + 1) * 4, hipMemcpyHostToDevice, s));
-            PFDR_HIP(hipMemcpyAsync(bVc.p, Vc, (size_t)V * 4, hipMemcpyHostToDevice, s));
-            dptr = bptr.p;
-            dVc = bVc.p;
-        }
+        CpPartition part(rV, rVc, V, Vc, dev, s);
+        const int *dptr = part.rVc, *dVc = part.Vc;
         auto out = [&](DevBuf<real> &b, real *h, size_t n) -> real * {
             if (dev && h) return h;
             b.alloc(n ? n : 1);
@@ -298,7 +304,7 @@ static int cp_reduce_host(const char *fn, int N, int V, const real *A, const rea
 template <typename real>
 int cp_reduce_sparse(CpCsc<real> &A, const real *Y, int rV, const int *rVc, const int *Vc,
                      int preAt, real *rA, real *rAA, real *rY, real *L) {
-    return cp_reduce_host<real>("pfdr_cp_reduce_csc", A.N, A.V, nullptr, Y, rV, rVc, Vc, preAt,
+    return cp_reduce_host<real>("pfdr_cp_reduce_csc", A.m.N, A.m.V, nullptr, Y, rV, rVc, Vc, preAt,
                                 PFDR_MEM_DEVICE, real(1e-3), 100, 10, rA, rAA, rY, L, nullptr,
                                 &A);
 }
@@ -339,11 +345,7 @@ long cp_reduce_sparse_direct(CpCsc<real> &A, int rV, const int *rVc, const int *
     const long bad = rA.colnorm(l, s);
     if (bad >= 0) return bad;
     rA.scale(l, 0, s);
-    SparseView<real> view;
-    view.N = rA.N, view.V = rV, view.nnz = rA.rnnz;
-    view.colptr = rA.colptr.p, view.rowidx = rA.rowidx.p, view.val = rA.val.p;
-    view.rowptr = rA.rowptr.p, view.colidx = rA.colidx.p, view.rval = rA.rval.p;
-    const real c = operator_norm_sparse<real>(view, normTol, normItMax, normNbInit, 0, s);
+    const real c = operator_norm_sparse<real>(rA.m, normTol, normItMax, normNbInit, 0, s);
     rA.scale(l, 1, s);
     k_cp_lipschitz<real><<<grid_for(rV), kBlock, 0, s>>>(rV, l, c, L);
     PFDR_HIP(hipGetLastError());
@@ -375,16 +377,8 @@ static int cp_reduce_csc_sparse(const char *fn, int N, int V, const pfdr_csc *A,
         const bool dev = mem == PFDR_MEM_DEVICE;
         CpCsc<real> sp;
         sp.take(N, V, A, mem, s);
-        DevBuf<int> bptr, bVc;
-        const int *dptr = rVc, *dVc = Vc;
-        if (!dev) {
-            bptr.alloc(rV + 1);
-            bVc.alloc(V);
-            PFDR_HIP(hipMemcpyAsync(bptr.p, rVc, (rV + 1) * 4, hipMemcpyHostToDevice, s));
-            PFDR_HIP(hipMemcpyAsync(bVc.p, Vc, (size_t)V * 4, hipMemcpyHostToDevice, s));
-            dptr = bptr.p;
-            dVc = bVc.p;
-        }
+        CpPartition part(rV, rVc, V, Vc, dev, s);
+        const int *dptr = part.rVc, *dVc = part.Vc;
         CpReduced<real> r;
         DevBuf<real> l(rV), dL(rV);
         const long bad = cp_reduce_sparse_direct<real>(sp, rV, dptr, dVc, normTol, normItMax,
@@ -396,10 +390,10 @@ static int cp_reduce_csc_sparse(const char *fn, int N, int V, const pfdr_csc *A,
             return report_error(fn, msg.c_str());
         }
         const auto k = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        *rnnz = r.rnnz;
-        PFDR_HIP(hipMemcpyAsync(rcolptr, r.colptr.p, ((size_t)rV + 1) * 8, k, s));
-        PFDR_HIP(hipMemcpyAsync(rrowidx, r.rowidx.p, (size_t)r.rnnz * 4, k, s));
-        PFDR_HIP(hipMemcpyAsync(rval, r.val.p, (size_t)r.rnnz * sizeof(real), k, s));
+        *rnnz = r.m.nnz;
+        PFDR_HIP(hipMemcpyAsync(rcolptr, r.m.colptr.p, ((size_t)rV + 1) * 8, k, s));
+        PFDR_HIP(hipMemcpyAsync(rrowidx, r.m.rowidx.p, (size_t)r.m.nnz * 4, k, s));
+        PFDR_HIP(hipMemcpyAsync(rval, r.m.val.p, (size_t)r.m.nnz * sizeof(real), k, s));
         if (L) PFDR_HIP(hipMemcpyAsync(L, dL.p, rV * sizeof(real), k, s));
         if (Leq) PFDR_HIP(hipMemcpyAsync(Leq, l.p, rV * sizeof(real), k, s));
         PFDR_HIP(hipStreamSynchronize(s));

@@ -19,7 +19,7 @@
 //       sorted order (rows ascending, and inside a row the components
 //       ascending, since a component's positions are one range of Vc); the
 //       head's lane adds its run as in 3 and stores (component, sum) at h:
-//       the CSR view, its row offsets written by the head that opens a row;
+//       the CSR view, its row offsets from the heads' rows (sorted_offsets);
 //   4'. the pairs (component, h) are sorted by component, stably, so a
 //       column's rows ascend strictly: the CSC.
 // A run is stored whatever its sum (a cancellation is a stored zero), so the
@@ -28,50 +28,12 @@
 // the dense kernels' order (k_cp_colnorm, k_cp_scale_cols, k_cpq_residual).
 //
 // Gradient: one lane per column, products formed, then added in stored order.
-#include <algorithm>
-#include <stdexcept>
-
 #include "pfdr_cp_sparse.hpp"
 #include "pfdr_sort.hpp"
 
 namespace pfdr {
 
 namespace {
-
-enum : unsigned { kBadColptr = 1u, kBadRow = 2u, kBadOrder = 4u };
-
-// colptr[0] = 0, colptr[V] = nnz, non-decreasing (threads 0 .. V); every row
-// index in [0, N) and above its predecessor in the same column (threads
-// 0 .. nnz - 1).  ecol[e] by a binary search that stays inside colptr[0 .. V)
-// whatever it holds.
-__global__ __launch_bounds__(256) void k_cpsp_check(int V, int N, int64_t nnz,
-                                                    const int64_t *__restrict__ colptr,
-                                                    const int *__restrict__ rowidx,
-                                                    int *__restrict__ ecol,
-                                                    unsigned *__restrict__ word) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned bad = 0;
-    if (t <= V) {
-        const int64_t c = colptr[t];
-        if (c < 0 || c > nnz) bad |= kBadColptr;
-        if (t == 0 && c != 0) bad |= kBadColptr;
-        if (t == V && c != nnz) bad |= kBadColptr;
-        if (t < V && colptr[t + 1] < c) bad |= kBadColptr;
-    }
-    if (t < nnz) {
-        int lo = 0, hi = V;  // the largest v in [0, V) with colptr[v] <= t
-        while (hi - lo > 1) {
-            const int mid = lo + (hi - lo) / 2;
-            if (colptr[mid] <= t) lo = mid;
-            else hi = mid;
-        }
-        ecol[t] = lo;
-        const int r = rowidx[t];
-        if (r < 0 || r >= N) bad |= kBadRow;
-        if (t > 0 && t > colptr[lo] && rowidx[t - 1] >= r) bad |= kBadOrder;
-    }
-    if (bad) atomicOr(word, bad);
-}
 
 // ---- an exclusive scan of len(0), len(1), ... over the positions 0 .. n
 // (len = 0 from n on), 16 per lane, a chunk of 4096 per workgroup.  Two
@@ -227,7 +189,26 @@ __global__ __launch_bounds__(256) void k_cpsp_gather(int64_t nnz, const unsigned
     sc[p] = cv[ecol[e]];
 }
 
-// the first entry of a (row, component) run adds the run in order
+// The sequential sum of the (row, component) run that sorted entry p opens:
+// a += sv[q], q ascending from p, from +0.  False where p opens no run.
+template <typename real>
+__device__ __forceinline__ bool cpsp_run(int64_t p, int64_t nnz, const unsigned *__restrict__ rows,
+                                         const int *__restrict__ sc, const real *__restrict__ sv,
+                                         unsigned &r, int &c, real &a) {
+    if (p >= nnz) return false;
+    r = rows[p];
+    c = sc[p];
+    if (p > 0 && rows[p - 1] == r && sc[p - 1] == c) return false;
+    a = real(0);
+    int64_t q = p;
+    do {
+        a += sv[q];
+        q++;
+    } while (q < nnz && rows[q] == r && sc[q] == c);
+    return true;
+}
+
+// every run's sum into its element of the zeroed dense rA
 template <typename real>
 __global__ __launch_bounds__(256) void k_cpsp_runs(int64_t nnz, int N,
                                                    const unsigned *__restrict__ rows,
@@ -235,23 +216,16 @@ __global__ __launch_bounds__(256) void k_cpsp_runs(int64_t nnz, int N,
                                                    const real *__restrict__ sv,
                                                    real *__restrict__ rA) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    const unsigned r = rows[p];
-    const int c = sc[p];
-    if (p > 0 && rows[p - 1] == r && sc[p - 1] == c) return;
-    real a = real(0);
-    int64_t q = p;
-    do {
-        a += sv[q];
-        q++;
-    } while (q < nnz && rows[q] == r && sc[q] == c);
-    rA[(size_t)N * c + r] = a;
+    unsigned r;
+    int c;
+    real a;
+    if (cpsp_run<real>(p, nnz, rows, sc, sv, r, c, a)) rA[(size_t)N * c + r] = a;
 }
 
 // ---- the reduced operator kept sparse (CpReduced)
-// k_cpsp_runs with the sum stored at the run's number h = pos[p] instead of a
-// dense element: CSR column and value of entry h, its row, and the (component,
-// h) pair that the sort by component takes
+// every run's sum at the run's number h = pos[p]: CSR column and value of
+// entry h, its row, and the (component, h) pair that the sort by component
+// takes
 template <typename real>
 __global__ __launch_bounds__(256) void k_cpsp_runs_csr(int64_t nnz,
                                                        const unsigned *__restrict__ rows,
@@ -264,36 +238,16 @@ __global__ __launch_bounds__(256) void k_cpsp_runs_csr(int64_t nnz,
                                                        unsigned *__restrict__ keys,
                                                        unsigned *__restrict__ vals) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    const unsigned r = rows[p];
-    const int c = sc[p];
-    if (p > 0 && rows[p - 1] == r && sc[p - 1] == c) return;
-    real a = real(0);
-    int64_t q = p;
-    do {
-        a += sv[q];
-        q++;
-    } while (q < nnz && rows[q] == r && sc[q] == c);
+    unsigned r;
+    int c;
+    real a;
+    if (!cpsp_run<real>(p, nnz, rows, sc, sv, r, c, a)) return;
     const int64_t h = pos[p];
     colidx[h] = c;
     rval[h] = a;
     hrow[h] = r;
     keys[h] = (unsigned)c;
     vals[h] = (unsigned)h;
-}
-
-// ptr[q] = the first of the n sorted ids that is >= q, q = 0 .. m: written by
-// the position that opens an id, and the tail by the last position
-__global__ __launch_bounds__(256) void k_cpsp_offsets(int64_t n, long m,
-                                                      const unsigned *__restrict__ id,
-                                                      int64_t *__restrict__ ptr) {
-    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= n) return;
-    const long r = (long)id[h];
-    const long prev = h ? (long)id[h - 1] : -1L;
-    for (long q = prev + 1; q <= r && q <= m; q++) ptr[q] = h;
-    if (h == n - 1)
-        for (long q = r + 1; q <= m; q++) ptr[q] = n;
 }
 
 // the CSC from the heads sorted by component (comp[j], head[j])
@@ -414,51 +368,10 @@ __global__ __launch_bounds__(256) void k_cpsp_grad(int V, const int64_t *__restr
 
 }  // namespace
 
-const char *cp_csc_args(const pfdr_csc *A) {
-    if (!A) return "sparse A: the pfdr_csc is NULL";
-    if (!A->colptr || !A->rowidx || !A->val) return "sparse A: a NULL array";
-    if (A->nnz < 1 || A->nnz >= 2147483648LL - 256)
-        return "sparse A: nnz must lie in [1, 2^31 - 256)";
-    return nullptr;
-}
-
-template <typename real>
-void CpCsc<real>::take(int N_, int V_, const pfdr_csc *A, int mem, hipStream_t s) {
-    N = N_, V = V_, nnz = A->nnz;
-    colptr.alloc((size_t)V + 1);
-    rowidx.alloc(nnz);
-    val.alloc(nnz);
-    ecol.alloc(nnz);
-    DevBuf<unsigned> word(1);
-    HostPins pins(s);
-    auto in = [&](void *dst, const void *src, size_t b) {
-        if (mem == PFDR_MEM_DEVICE)
-            PFDR_HIP(hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToDevice, s));
-        else
-            pins.copy(dst, src, b, hipMemcpyHostToDevice);
-    };
-    in(colptr.p, A->colptr, ((size_t)V + 1) * 8);
-    in(rowidx.p, A->rowidx, (size_t)nnz * 4);
-    in(val.p, A->val, (size_t)nnz * sizeof(real));
-    PFDR_HIP(hipMemsetAsync(word.p, 0, sizeof(unsigned), s));
-    k_cpsp_check<<<grid_for(std::max<long>((long)V + 1, (long)nnz)), kBlock, 0, s>>>(
-        V, N, nnz, colptr.p, rowidx.p, ecol.p, word.p);
-    PFDR_HIP(hipGetLastError());
-    unsigned w = 0;
-    PFDR_HIP(hipMemcpyAsync(&w, word.p, sizeof w, hipMemcpyDeviceToHost, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    pins.release();
-    if (w & kBadColptr)
-        throw std::runtime_error("sparse A: colptr must be non-decreasing with colptr[0] = 0 "
-                                 "and colptr[V] = nnz");
-    if (w & kBadRow) throw std::runtime_error("sparse A: row index outside [0, N)");
-    if (w & kBadOrder)
-        throw std::runtime_error("sparse A: row indices must be strictly ascending inside "
-                                 "each column");
-}
-
 template <typename real>
 void CpCsc<real>::sort_entries(int rV, const int *rVc, const int *Vc, hipStream_t s) {
+    const int N = m.N, V = m.V;
+    const int64_t nnz = m.nnz;
     if (!ki.p) {
         off.alloc((size_t)V + 1);
         sums.alloc(((size_t)V + kChunk) / kChunk);
@@ -468,24 +381,22 @@ void CpCsc<real>::sort_entries(int rV, const int *rVc, const int *Vc, hipStream_
         ki.alloc(nnz), ko.alloc(nnz), vi.alloc(nnz), vo.alloc(nnz);
     }
     PFDR_HIP(hipMemsetAsync(cv.p, 0, sizeof(int) * (size_t)V, s));
-    cpsp_scan(V, CpspColLen{V, colptr.p, Vc}, sums.p, off.p, s);
+    cpsp_scan(V, CpspColLen{V, m.colptr.p, Vc}, sums.p, off.p, s);
     k_cpsp_comp<<<grid_for(V), kBlock, 0, s>>>(V, rV, rVc, Vc, cv.p);
-    k_cpsp_keys<<<grid_for(nnz), kBlock, 0, s>>>(V, nnz, off.p, colptr.p, Vc, rowidx.p, ki.p,
+    k_cpsp_keys<<<grid_for(nnz), kBlock, 0, s>>>(V, nnz, off.p, m.colptr.p, Vc, m.rowidx.p, ki.p,
                                                  vi.p);
     PFDR_HIP(hipGetLastError());
-    int bits = 1;
-    while (bits < 32 && (1L << bits) < (long)N) bits++;
-    radix_sort_pairs_stable<unsigned>(ki.p, ko.p, vi.p, vo.p, (long)nnz, bits, s);
-    k_cpsp_gather<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, vo.p, ecol.p, cv.p, val.p, sv.p,
+    radix_sort_pairs_stable<unsigned>(ki.p, ko.p, vi.p, vo.p, (long)nnz, radix_key_bits(N), s);
+    k_cpsp_gather<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, vo.p, m.ecol.p, cv.p, m.val.p, sv.p,
                                                          sc.p);
     PFDR_HIP(hipGetLastError());
 }
 
 template <typename real>
 void CpCsc<real>::colsum(int rV, const int *rVc, const int *Vc, real *rA, hipStream_t s) {
-    PFDR_HIP(hipMemsetAsync(rA, 0, sizeof(real) * (size_t)N * rV, s));
+    PFDR_HIP(hipMemsetAsync(rA, 0, sizeof(real) * (size_t)m.N * rV, s));
     sort_entries(rV, rVc, Vc, s);
-    k_cpsp_runs<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, N, ko.p, sc.p, sv.p, rA);
+    k_cpsp_runs<real><<<grid_for(m.nnz), kBlock, 0, s>>>(m.nnz, m.N, ko.p, sc.p, sv.p, rA);
     PFDR_HIP(hipGetLastError());
 }
 
@@ -493,6 +404,8 @@ template <typename real>
 void CpCsc<real>::reduced(int rV, const int *rVc, const int *Vc, CpReduced<real> &out,
                           hipStream_t s) {
     sort_entries(rV, rVc, Vc, s);
+    const int N = m.N;
+    const int64_t nnz = m.nnz;
     if (!pos.p) {
         pos.alloc((size_t)nnz + 1);
         psums.alloc(((size_t)nnz + kChunk) / kChunk);
@@ -504,25 +417,24 @@ void CpCsc<real>::reduced(int rV, const int *rVc, const int *Vc, CpReduced<real>
     int64_t rnnz = 0;
     PFDR_HIP(hipMemcpyAsync(&rnnz, pos.p + nnz, sizeof rnnz, hipMemcpyDeviceToHost, s));
     PFDR_HIP(hipStreamSynchronize(s));
-    out.N = N, out.rV = rV, out.rnnz = rnnz;
-    out.rowptr.alloc((size_t)N + 1);
-    out.colptr.alloc((size_t)rV + 1);
-    out.colidx.alloc(rnnz), out.rval.alloc(rnnz);
-    out.rowidx.alloc(rnnz), out.ecol.alloc(rnnz), out.val.alloc(rnnz);
+    DevCsc<real> &o = out.m;
+    o.N = N, o.V = rV, o.nnz = rnnz;
+    o.rowptr.alloc((size_t)N + 1);
+    o.colptr.alloc((size_t)rV + 1);
+    o.colidx.alloc(rnnz), o.rval.alloc(rnnz);
+    o.rowidx.alloc(rnnz), o.ecol.alloc(rnnz), o.val.alloc(rnnz);
     // CSR: the heads in sorted order (rows ascending, components ascending inside a row)
     k_cpsp_runs_csr<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, ko.p, sc.p, sv.p, pos.p,
-                                                           out.colidx.p, out.rval.p, hrow.p, ki.p,
+                                                           o.colidx.p, o.rval.p, hrow.p, ki.p,
                                                            vi.p);
-    k_cpsp_offsets<<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, N, hrow.p, out.rowptr.p);
     PFDR_HIP(hipGetLastError());
+    sorted_offsets(rnnz, N, hrow.p, o.rowptr.p, s);
     // CSC: the heads sorted by component, stably, so that a column's rows ascend
-    int bits = 1;
-    while (bits < 32 && (1L << bits) < (long)rV) bits++;
-    radix_sort_pairs_stable<unsigned>(ki.p, ko.p, vi.p, vo.p, (long)rnnz, bits, s);
-    k_cpsp_csc_fill<real><<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, ko.p, vo.p, hrow.p, out.rval.p,
-                                                            out.rowidx.p, out.ecol.p, out.val.p);
-    k_cpsp_offsets<<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, rV, ko.p, out.colptr.p);
+    radix_sort_pairs_stable<unsigned>(ki.p, ko.p, vi.p, vo.p, (long)rnnz, radix_key_bits(rV), s);
+    k_cpsp_csc_fill<real><<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, ko.p, vo.p, hrow.p, o.rval.p,
+                                                            o.rowidx.p, o.ecol.p, o.val.p);
     PFDR_HIP(hipGetLastError());
+    sorted_offsets(rnnz, rV, ko.p, o.colptr.p, s);
 }
 
 template <typename real>
@@ -531,7 +443,7 @@ long CpReduced<real>::colnorm(real *l, hipStream_t s) const {
     const int none = 0x7fffffff;
     int first = none;
     PFDR_HIP(hipMemcpyAsync(bad.p, &none, sizeof none, hipMemcpyHostToDevice, s));
-    k_cpsp_colnorm<real><<<grid_for(rV), kBlock, 0, s>>>(rV, colptr.p, val.p, l, bad.p);
+    k_cpsp_colnorm<real><<<grid_for(m.V), kBlock, 0, s>>>(m.V, m.colptr.p, m.val.p, l, bad.p);
     PFDR_HIP(hipGetLastError());
     PFDR_HIP(hipMemcpyAsync(&first, bad.p, sizeof first, hipMemcpyDeviceToHost, s));
     PFDR_HIP(hipStreamSynchronize(s));
@@ -540,20 +452,22 @@ long CpReduced<real>::colnorm(real *l, hipStream_t s) const {
 
 template <typename real>
 void CpReduced<real>::scale(const real *l, int mul, hipStream_t s) {
-    k_cpsp_scale<real><<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, ecol.p, l, val.p, mul);
-    k_cpsp_scale<real><<<grid_for(rnnz), kBlock, 0, s>>>(rnnz, colidx.p, l, rval.p, mul);
+    k_cpsp_scale<real><<<grid_for(m.nnz), kBlock, 0, s>>>(m.nnz, m.ecol.p, l, m.val.p, mul);
+    k_cpsp_scale<real><<<grid_for(m.nnz), kBlock, 0, s>>>(m.nnz, m.colidx.p, l, m.rval.p, mul);
     PFDR_HIP(hipGetLastError());
 }
 
 template <typename real>
 void CpReduced<real>::residual(const real *rX, const real *Y, real *R, hipStream_t s) const {
-    k_cpsp_residual<real><<<grid_for(N), kBlock, 0, s>>>(N, rowptr.p, colidx.p, rval.p, rX, Y, R);
+    k_cpsp_residual<real><<<grid_for(m.N), kBlock, 0, s>>>(m.N, m.rowptr.p, m.colidx.p, m.rval.p,
+                                                           rX, Y, R);
     PFDR_HIP(hipGetLastError());
 }
 
 template <typename real>
 void CpCsc<real>::gradient(const real *R, real *DfS, hipStream_t s) const {
-    k_cpsp_grad<real><<<grid_for(V), kBlock, 0, s>>>(V, colptr.p, rowidx.p, val.p, R, DfS);
+    k_cpsp_grad<real><<<grid_for(m.V), kBlock, 0, s>>>(m.V, m.colptr.p, m.rowidx.p, m.val.p, R,
+                                                       DfS);
     PFDR_HIP(hipGetLastError());
 }
 

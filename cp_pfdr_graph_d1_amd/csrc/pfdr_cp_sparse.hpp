@@ -7,6 +7,7 @@
 //             (CpReduced), for the direct branch of pfdr_cp_reduce
 //   gradient  DfS = -A^t R, the base of pfdr_cpgraph_gradient for N > 0
 //   take      the copy and the structural checks of a caller's pfdr_csc
+//             (DevCsc, pfdr_spmat.hpp)
 // Every sum adds the stored entries only, from +0, in the order the dense
 // loops add the whole column or row -- the argument of pfdr_sparse.hpp: the
 // skipped terms are +-0 -- so they give the dense kernels' bytes on the
@@ -14,22 +15,18 @@
 // downstream of a CpReduced run its own column norms, scaling and residual,
 // which skip +-0 terms in the same way.
 #pragma once
-#include "pfdr_dev.hpp"
+#include "pfdr_spmat.hpp"
 
 namespace pfdr {
 
 // The reduced operator rA (N-by-rV) on the device: a CSC (columns =
 // components, rows strictly ascending inside a column) and its CSR view (the
-// columns of a row ascending).  A pair (n, rv) is stored iff A stores some
-// entry A[n, v] with v in component rv, whatever the sum comes to.
+// columns of a row ascending), both filled by CpCsc::reduced; ecol is kept.
+// A pair (n, rv) is stored iff A stores some entry A[n, v] with v in
+// component rv, whatever the sum comes to.
 template <typename real>
 struct CpReduced {
-    int N = 0, rV = 0;
-    int64_t rnnz = 0;
-    DevBuf<int64_t> colptr, rowptr;  // rV + 1, N + 1
-    DevBuf<int> rowidx, ecol;        // CSC: the row / the column of stored entry j
-    DevBuf<int> colidx;              // CSR: the column of stored entry h
-    DevBuf<real> val, rval;          // CSC / CSR values
+    DevCsc<real> m;  // V = rV, nnz = rnnz
 
     // l[rv] = sqrt of the squares of column rv's values added in ascending row
     // order from +0 (k_cp_colnorm's order).  Returns the first rv whose l is 0
@@ -40,24 +37,21 @@ struct CpReduced {
     // R[n] = Y[n] - (sum of rval * rX[colidx] over row n's entries, rv
     // ascending, from +0): k_cpq_residual's bytes on the densified rA
     void residual(const real *rX, const real *Y, real *R, hipStream_t s) const;
-    pfdr_csc csc() const { return pfdr_csc{rnnz, colptr.p, rowidx.p, val.p}; }
+    pfdr_csc csc() const { return pfdr_csc{m.nnz, m.colptr.p, m.rowidx.p, m.val.p}; }
 };
-
-// The checks of a pfdr_csc that need no device (NULL arrays, nnz): the
-// offence, or nullptr.
-const char *cp_csc_args(const pfdr_csc *A);
 
 template <typename real>
 struct CpCsc {
-    int N = 0, V = 0;
-    int64_t nnz = 0;
-    DevBuf<int64_t> colptr;
-    DevBuf<int> rowidx, ecol;  // ecol[e]: the column of entry e
-    DevBuf<real> val;
+    DevCsc<real> m;  // the checked copy and its ecol; no CSR view of A is built
 
     // Copies A in (host or device per mem) and checks it on the device: throws
     // std::runtime_error naming the offence.
-    void take(int N_, int V_, const pfdr_csc *A, int mem, hipStream_t s);
+    void take(int N, int V, const pfdr_csc *A, int mem, hipStream_t s) {
+        HostPins pins(s);
+        m.take(N, V, A, mem, s, pins);
+        pins.release();
+        m.word.release();  // (a session's later check keeps it; nothing here reads it again)
+    }
     // rA[n + N rv] = the stored entries A[n, Vc[i]], i = rVc[rv] ... rVc[rv + 1] - 1
     // ascending, added from +0; 0 where there is none.  Device arrays; rVc =
     // nullptr: one component, Vc = nullptr: the identity.  The scratch (a sort

@@ -1467,7 +1467,7 @@ struct CpGraph : CpGraphBase {
     void gradient_sparse(const void *A, const void *R) override {
         if (!rX.p) throw std::runtime_error("gradient: set the component values first");
         const auto &sp = *(const CpCsc<real> *)A;
-        if (sp.V != V || !R) throw std::runtime_error("gradient: a sparse A needs V columns and R");
+        if (sp.m.V != V || !R) throw std::runtime_error("gradient: a sparse A needs V columns and R");
         DfS.alloc(V);
         sp.gradient((const real *)R, DfS.p, s);
         k_cp_grad<real><<<grid_for(V), kBlock, 0, s>>>(V, 2, nullptr, nullptr, inc.ptr.p, inc.idx.p,

@@ -286,7 +286,7 @@ struct QuadDriver : CpDriverBase {
 
     // component column sums (and, preAt, the reduced normal equations) of pfdr_cp_reduce
     void reduce(int preAt, real *rA, real *rAA, real *rY, real *L) {
-        if (sp.nnz)
+        if (sp.m.nnz)
             CP_ABI(cp_reduce_sparse<real>(sp, dY.p, rV, drVc.p, dVc.p, preAt, rA, rAA, rY, L));
         else if (sizeof(real) == 4)
             CP_ABI(pfdr_cp_reduce_f32(N, V, (const float *)pA, (const float *)dY.p, rV, drVc.p,
@@ -342,7 +342,7 @@ struct QuadDriver : CpDriverBase {
         }
         obj_known = false;
     }
-    bool holds_sparse_A() const override { return sp.nnz > 0; }
+    bool holds_sparse_A() const override { return sp.m.nnz > 0; }
     const void *values() const override { return drX.p; }
     const void *residual() const override { return N > 0 ? dR.p : nullptr; }
     void forget_objective() override { obj_known = false; }
@@ -421,7 +421,7 @@ struct QuadDriver : CpDriverBase {
             if (it == CP_itMax || dif < difTol2) break;
             // steepest cuts (l1 :337-556 / bounds :331-529)
             t = clock::now();
-            if (sp.nnz)
+            if (sp.m.nnz)
                 CP_ABI(cpgraph_gradient_sparse(g, &sp, dR.p));
             else
                 CP_ABI(pfdr_cpgraph_gradient(g, N, pA, dY.p, N > 0 ? dR.p : nullptr,
@@ -491,7 +491,7 @@ struct QuadDriver : CpDriverBase {
             }
             if (sparse_rA) {
                 sparse_its++;
-                if (rs.rnnz > max_rnnz) max_rnnz = rs.rnnz;
+                if (rs.m.nnz > max_rnnz) max_rnnz = rs.m.nnz;
             } else if (!preAt) {
                 dense_direct_its++;
             }

@@ -11,7 +11,6 @@
 #include "pfdr_quadratic_kernels.hpp"
 #include "pfdr_sort.hpp"
 #include "pfdr_sparse.hpp"
-#include "pfdr_sparse_view.hpp"
 
 namespace pfdr {
 
@@ -476,10 +475,10 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool 
     if (sparse_) {  // checked copy of the CSC, CSR view, kernel family
         sp_.setup(V_, N_, csc, mem, kExactChain, s, pins_);
         sparse_exact = sp_.exact ? 1 : 0;
-        sparse_nnz = sp_.nnz;
+        sparse_nnz = sp_.m.nnz;
         sparse_seg_col = sp_.gc;
         sparse_seg_row = sp_.gr;
-        sparse_csr_us = (int64_t)(sp_.csr_ms * 1e3);
+        sparse_csr_us = (int64_t)(sp_.m.csr_ms * 1e3);
     }
     if (reordered_) {  // into the internal labels (identity / diagonal A only)
         permute(A_, order_.p, V, s);
@@ -544,9 +543,11 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool 
         }
         prof.on = pon;
         if (sparse_) {
-            k_sp_norm_check<real><<<grid_for(V), kBlock, 0, s>>>(V_, diag_.p, sp_.word.p);
+            k_sp_norm_check<real><<<grid_for(V), kBlock, 0, s>>>(V_, diag_.p, sp_.m.word.p);
             PFDR_HIP(hipGetLastError());
-            sp_throw(sp_.verdict(s));
+            if (sp_.m.verdict(s))
+                throw std::runtime_error("sparse A: a column has squared norm 0 (the reference "
+                                         "divides by it)");
         }
     } else {
         k_diag<real><<<grid_for(V), kBlock, 0, s>>>(V_, mode_, A_.p, Vglob_, v0_, diag_.p);
@@ -1972,30 +1973,6 @@ static int quadratic_host(const char *fn, int kind, int V, int E, int N, real *X
     p.itMax = itMax; p.verbose = verbose;
     return solve_one_call<QuadSession<real>>(fn, p, X, it, Obj, Dif, N, 1, !csc, csc);
 }
-
-// pfdr_sparse_view.hpp: a SparseOp set up as a session sets its own up, kept
-// by the owner handed back (the kernel family it chose is not used)
-template <typename real>
-std::shared_ptr<void> sparse_view(int N, int V, const pfdr_csc *A, int mem, hipStream_t s,
-                                  SparseView<real> &out) {
-    auto op = std::make_shared<SparseOp<real>>();
-    {
-        HostPins pins(s);
-        op->setup(V, N, A, mem, 0, s, pins);
-        pins.release();
-    }
-    out.N = N; out.V = V; out.nnz = op->nnz;
-    out.colptr = op->colptr.p; out.rowptr = op->rowptr.p;
-    out.rowidx = op->rowidx.p; out.colidx = op->colidx.p;
-    out.val = op->val.p; out.rval = op->rval.p;
-    out.maxcol = op->maxcol; out.maxrow = op->maxrow;
-    out.csr_ms = op->csr_ms;
-    return op;
-}
-template std::shared_ptr<void> sparse_view<float>(int, int, const pfdr_csc *, int, hipStream_t,
-                                                  SparseView<float> &);
-template std::shared_ptr<void> sparse_view<double>(int, int, const pfdr_csc *, int, hipStream_t,
-                                                   SparseView<double> &);
 
 }  // namespace pfdr
 

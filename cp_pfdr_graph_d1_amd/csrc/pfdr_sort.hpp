@@ -30,4 +30,11 @@ template <typename K>
 void radix_sort_pairs_stable(const K *kin, K *kout, const unsigned *vin, unsigned *vout, long n,
                              int bits, hipStream_t s);
 
+// key width of 32-bit ids 0 .. n - 1: the smallest bits in [1, 32] with 2^bits >= n
+inline int radix_key_bits(long n) {
+    int bits = 1;
+    while (bits < 32 && (1L << bits) < n) bits++;
+    return bits;
+}
+
 }  // namespace pfdr

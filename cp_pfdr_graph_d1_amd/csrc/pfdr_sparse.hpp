@@ -21,18 +21,17 @@
 //       double (dacc), a shuffle reduction inside the segment.
 // The value and index streams are read coalesced (consecutive lanes of a
 // segment read consecutive entries); w, R and xp are gathered.
+//
+// Templates and inlines only, on top of pfdr_quadratic_kernels.hpp's gates and
+// epilogues (so for pfdr_quadratic.hip); the matrix, its content check and
+// its CSR build are DevCsc's (pfdr_spmat.hpp), which any unit may include.
 #pragma once
-#include <chrono>
 #include <string>
 
 #include "pfdr_quadratic_kernels.hpp"
-#include "pfdr_sort.hpp"
+#include "pfdr_spmat.hpp"
 
 namespace pfdr {
-
-// content checks of a CSC, folded into one word
-enum SpBad : unsigned { SP_BAD_COLPTR = 1u, SP_BAD_ROW = 2u, SP_BAD_ORDER = 4u,
-                        SP_BAD_NORM = 8u };
 
 template <typename real>
 struct SpArgs {
@@ -42,85 +41,12 @@ struct SpArgs {
     ColArgs<real> c;     // ncols segments; A and len unused
 };
 
-// One pass over colptr (threads 0 .. V) and rowidx (threads 0 .. nnz - 1):
-// colptr[0] = 0, colptr[V] = nnz, non-decreasing; every row index in [0, N)
-// and above its predecessor in the same column.  ecol[e] = the column of
-// entry e (the CSR build's column indices), by a binary search that stays
-// inside colptr[0 .. V] whatever it holds.
-__global__ __launch_bounds__(256) void k_sp_check(int V, int N, int64_t nnz,
-                                                  const int64_t *__restrict__ colptr,
-                                                  const int *__restrict__ rowidx,
-                                                  int *__restrict__ ecol,
-                                                  unsigned *__restrict__ word) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned bad = 0;
-    if (t <= V) {
-        const int64_t c = colptr[t];
-        if (c < 0 || c > nnz) bad |= SP_BAD_COLPTR;
-        if (t == 0 && c != 0) bad |= SP_BAD_COLPTR;
-        if (t == V && c != nnz) bad |= SP_BAD_COLPTR;
-        if (t < V && colptr[t + 1] < c) bad |= SP_BAD_COLPTR;
-    }
-    if (t < nnz) {
-        int lo = 0, hi = V;  // the largest v in [0, V) with colptr[v] <= t
-        while (hi - lo > 1) {
-            const int mid = lo + (hi - lo) / 2;
-            if (colptr[mid] <= t) lo = mid; else hi = mid;
-        }
-        ecol[t] = lo;
-        const int r = rowidx[t];
-        if (r < 0 || r >= N) bad |= SP_BAD_ROW;
-        if (t > 0 && t > colptr[lo] && rowidx[t - 1] >= r) bad |= SP_BAD_ORDER;
-    }
-    if (bad) atomicOr(word, bad);
-}
-
 // a column of squared norm 0: the reference divides by it (ref :96, :133)
 template <typename real>
 __global__ void k_sp_norm_check(int V, const real *__restrict__ diag,
                                 unsigned *__restrict__ word) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < V && diag[v] == real(0)) atomicOr(word, (unsigned)SP_BAD_NORM);
-}
-
-__global__ void k_sp_keys(int64_t nnz, const int *__restrict__ rowidx,
-                          unsigned *__restrict__ keys, unsigned *__restrict__ vals) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nnz) return;
-    keys[e] = (unsigned)rowidx[e];
-    vals[e] = (unsigned)e;
-}
-
-// the CSR arrays from the entries sorted by row (rows[p] = the row of sorted
-// position p, perm[p] = its entry): the sort is stable and the entries were
-// enumerated in column order, so every row's columns ascend.  rowptr[q] = the
-// first position of a row >= q, written by the position that opens it.
-template <typename real>
-__global__ __launch_bounds__(256) void k_sp_csr_fill(int64_t nnz, int N,
-                                                     const unsigned *__restrict__ rows,
-                                                     const unsigned *__restrict__ perm,
-                                                     const int *__restrict__ ecol,
-                                                     const real *__restrict__ val,
-                                                     int64_t *__restrict__ rowptr,
-                                                     int *__restrict__ colidx,
-                                                     real *__restrict__ rval) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    const unsigned e = perm[p];
-    colidx[p] = ecol[e];
-    rval[p] = val[e];
-    const long r = (long)rows[p];
-    const long prev = p ? (long)rows[p - 1] : -1L;
-    for (long q = prev + 1; q <= r; q++) rowptr[q] = p;
-    if (p == nnz - 1)
-        for (long q = r + 1; q <= N; q++) rowptr[q] = nnz;
-}
-
-// the longest segment of an offset array
-__global__ void k_sp_maxlen(int n, const int64_t *__restrict__ ptr, int *__restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    atomicMax(out, (int)(ptr[i + 1] - ptr[i]));
+    if (v < V && diag[v] == real(0)) atomicOr(word, 1u);
 }
 
 // ------------------------------------------------ sequential-order kernels --
@@ -264,115 +190,43 @@ inline int sp_exact_env() {
     throw std::runtime_error("PFDR_SPARSE_EXACT must be 1, 0 or auto");
 }
 
-// the first offence of a check word, by name
-inline void sp_throw(unsigned w) {
-    if (w & SP_BAD_COLPTR)
-        throw std::runtime_error("sparse A: colptr must be non-decreasing with colptr[0] = 0 "
-                                 "and colptr[V] = nnz");
-    if (w & SP_BAD_ROW) throw std::runtime_error("sparse A: row index outside [0, N)");
-    if (w & SP_BAD_ORDER)
-        throw std::runtime_error("sparse A: row indices must be strictly ascending inside "
-                                 "each column");
-    if (w & SP_BAD_NORM)
-        throw std::runtime_error("sparse A: a column has squared norm 0 (the reference "
-                                 "divides by it)");
-}
-
+// A session's operator: the matrix (pfdr_spmat.hpp) and the kernel family
+// that walks it.
 template <typename real>
 struct SparseOp {
-    int V = 0, N = 0;
-    int64_t nnz = 0;
-    DevBuf<int64_t> colptr, rowptr;
-    DevBuf<int> rowidx, colidx;
-    DevBuf<real> val, rval;
-    DevBuf<unsigned> word;  // the checks' flags
-    bool exact = false;     // sequential-order kernels
-    int gc = 4, gr = 4;     // lanes per column / row of the parallel kernels
-    int maxcol = 0, maxrow = 0;
-    double csr_ms = 0.0;    // wall time of the CSR build (sort included)
+    DevCsc<real> m;
+    bool exact = false;  // sequential-order kernels
+    int gc = 4, gr = 4;  // lanes per column / row of the parallel kernels
 
     size_t bytes() const {
-        return (colptr.n + rowptr.n) * 8 + (rowidx.n + colidx.n) * 4 +
-               (val.n + rval.n) * sizeof(real);
-    }
-
-    unsigned verdict(hipStream_t s) {
-        unsigned w = 0;
-        PFDR_HIP(hipMemcpyAsync(&w, word.p, sizeof w, hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-        return w;
+        return (m.colptr.n + m.rowptr.n) * 8 + (m.rowidx.n + m.colidx.n) * 4 +
+               (m.val.n + m.rval.n) * sizeof(real);
     }
 
     // copy the CSC in, check it, build the CSR view, choose the kernels
-    void setup(int V_, int N_, const pfdr_csc *A, int mem, long exact_chain, hipStream_t s,
+    void setup(int V, int N, const pfdr_csc *A, int mem, long exact_chain, hipStream_t s,
                HostPins &pins) {
-        V = V_; N = N_; nnz = A->nnz;
-        auto in = [&](void *dst, const void *src, size_t b) {
-            if (mem == PFDR_MEM_DEVICE)
-                PFDR_HIP(hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToDevice, s));
-            else
-                pins.copy(dst, src, b, hipMemcpyHostToDevice);
-        };
-        colptr.alloc((size_t)V + 1);
-        rowidx.alloc(nnz);
-        val.alloc(nnz);
-        in(colptr.p, A->colptr, ((size_t)V + 1) * 8);
-        in(rowidx.p, A->rowidx, (size_t)nnz * 4);
-        in(val.p, A->val, (size_t)nnz * sizeof(real));
-        word.alloc(1);
-        PFDR_HIP(hipMemsetAsync(word.p, 0, sizeof(unsigned), s));
-        DevBuf<int> ecol(nnz);
-        k_sp_check<<<grid_for(std::max<long>((long)V + 1, (long)nnz)), kBlock, 0, s>>>(
-            V, N, nnz, colptr.p, rowidx.p, ecol.p, word.p);
-        PFDR_HIP(hipGetLastError());
-        sp_throw(verdict(s));
-
-        const auto t0 = std::chrono::steady_clock::now();
-        rowptr.alloc((size_t)N + 1);
-        colidx.alloc(nnz);
-        rval.alloc(nnz);
-        {
-            DevBuf<unsigned> ki(nnz), ko(nnz), vi(nnz), vo(nnz);
-            k_sp_keys<<<grid_for(nnz), kBlock, 0, s>>>(nnz, rowidx.p, ki.p, vi.p);
-            PFDR_HIP(hipGetLastError());
-            int bits = 1;
-            while (bits < 32 && (1L << bits) < (long)N) bits++;
-            radix_sort_pairs_stable<unsigned>(ki.p, ko.p, vi.p, vo.p, (long)nnz, bits, s);
-            k_sp_csr_fill<real><<<grid_for(nnz), kBlock, 0, s>>>(nnz, N, ko.p, vo.p, ecol.p, val.p,
-                                                                rowptr.p, colidx.p, rval.p);
-            PFDR_HIP(hipGetLastError());
-            DevBuf<int> mx(2);
-            PFDR_HIP(hipMemsetAsync(mx.p, 0, 2 * sizeof(int), s));
-            k_sp_maxlen<<<grid_for(V), kBlock, 0, s>>>(V, colptr.p, mx.p);
-            k_sp_maxlen<<<grid_for(N), kBlock, 0, s>>>(N, rowptr.p, mx.p + 1);
-            PFDR_HIP(hipGetLastError());
-            int h[2] = {0, 0};
-            PFDR_HIP(hipMemcpyAsync(h, mx.p, sizeof h, hipMemcpyDeviceToHost, s));
-            PFDR_HIP(hipStreamSynchronize(s));
-            maxcol = h[0];
-            maxrow = h[1];
-        }
-        csr_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-                     .count();
+        m.take(N, V, A, mem, s, pins);
+        m.build_csr(s);
         const int forced = sp_exact_env();
-        exact = forced < 0 ? (maxcol <= exact_chain && maxrow <= exact_chain) : forced == 1;
-        gc = sp_segment((double)nnz / V);
-        gr = sp_segment((double)nnz / N);
+        exact = forced < 0 ? (m.maxcol <= exact_chain && m.maxrow <= exact_chain) : forced == 1;
+        gc = sp_segment((double)m.nnz / V);
+        gr = sp_segment((double)m.nnz / N);
     }
 
     template <int EPI, int G>
     void cols_g(const SpArgs<real> &a, hipStream_t s) {
-        k_spc_dot<real, EPI, G><<<grid_for((long)V * G), kBlock, 0, s>>>(a);
+        k_spc_dot<real, EPI, G><<<grid_for((long)m.V * G), kBlock, 0, s>>>(a);
     }
 
     // column dots with epilogue EPI (ca.ncols = V; ca.A and ca.len unused)
     template <int EPI>
     void cols(const ColArgs<real> &ca, hipStream_t s) {
-        SpArgs<real> a{colptr.p, rowidx.p, val.p, ca};
+        SpArgs<real> a{m.colptr.p, m.rowidx.p, m.val.p, ca};
         a.c.A = nullptr;
-        a.c.ncols = V;
+        a.c.ncols = m.V;
         if (exact) {
-            k_spc_seq<real, EPI><<<grid_for(V), kBlock, 0, s>>>(a);
+            k_spc_seq<real, EPI><<<grid_for(m.V), kBlock, 0, s>>>(a);
         } else {
             switch (gc) {
             case 4: cols_g<EPI, 4>(a, s); break;
@@ -388,16 +242,16 @@ struct SparseOp {
     template <int G>
     void rows_g(const R2<real> *xp, const real *Y, real *R, const Ctrl<real> *c, int gate,
                 hipStream_t s) {
-        k_spr_rows<real, G><<<grid_for((long)N * G), kBlock, 0, s>>>(N, rowptr.p, colidx.p, rval.p,
-                                                                    xp, Y, R, c, gate);
+        k_spr_rows<real, G><<<grid_for((long)m.N * G), kBlock, 0, s>>>(
+            m.N, m.rowptr.p, m.colidx.p, m.rval.p, xp, Y, R, c, gate);
     }
 
     // R = Y - A X
     void rows(const R2<real> *xp, const real *Y, real *R, const Ctrl<real> *c, int gate,
               hipStream_t s) {
         if (exact) {
-            k_spr_seq<real><<<grid_for(N), kBlock, 0, s>>>(N, rowptr.p, colidx.p, rval.p, xp, Y, R,
-                                                          c, gate);
+            k_spr_seq<real><<<grid_for(m.N), kBlock, 0, s>>>(m.N, m.rowptr.p, m.colidx.p, m.rval.p,
+                                                            xp, Y, R, c, gate);
         } else {
             switch (gr) {
             case 4: rows_g<4>(xp, Y, R, c, gate, s); break;
@@ -412,10 +266,10 @@ struct SparseOp {
 
     // the CSR view into host arrays (debug read-back)
     void read_csr(int64_t *rp, int32_t *ci, void *rv, hipStream_t s) const {
-        if (rp) PFDR_HIP(hipMemcpyAsync(rp, rowptr.p, ((size_t)N + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (ci) PFDR_HIP(hipMemcpyAsync(ci, colidx.p, (size_t)nnz * 4, hipMemcpyDeviceToHost, s));
-        if (rv) PFDR_HIP(hipMemcpyAsync(rv, rval.p, (size_t)nnz * sizeof(real),
-                                        hipMemcpyDeviceToHost, s));
+        const auto k = hipMemcpyDeviceToHost;
+        if (rp) PFDR_HIP(hipMemcpyAsync(rp, m.rowptr.p, ((size_t)m.N + 1) * 8, k, s));
+        if (ci) PFDR_HIP(hipMemcpyAsync(ci, m.colidx.p, (size_t)m.nnz * 4, k, s));
+        if (rv) PFDR_HIP(hipMemcpyAsync(rv, m.rval.p, (size_t)m.nnz * sizeof(real), k, s));
         PFDR_HIP(hipStreamSynchronize(s));
     }
 };

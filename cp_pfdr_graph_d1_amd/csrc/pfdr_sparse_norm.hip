@@ -5,8 +5,8 @@
 //   pfdr_lipschitz_diag_csc_*  the diagonal majorant L[v] = sum_i |A_iv| r_i,
 //       r_i = sum_j |A_ij| (A^tA <= diag(L) by Cauchy-Schwarz), and the scalar
 //       bound ||A||_1 ||A||_inf.
-// The checked copy of the CSC and its CSR view come from sparse_view
-// (pfdr_sparse_view.hpp); the stopping rule and the starting values are the
+// The checked copy of the CSC and its CSR view are a DevCsc
+// (pfdr_spmat.hpp); the stopping rule and the starting values are the
 // dense entry's (pfdr_power.hpp).
 //
 // Power method: all starts of a batch of B = 16, 32 or 64 iterate at once, as
@@ -36,9 +36,8 @@
 #include <stdexcept>
 #include <vector>
 
-#include "pfdr_cp_sparse.hpp"
 #include "pfdr_power.hpp"
-#include "pfdr_sparse_view.hpp"
+#include "pfdr_spmat.hpp"
 
 namespace pfdr {
 
@@ -210,12 +209,21 @@ const char *csc_entry_args(int N, int V, const pfdr_csc *A, int mem) {
     return cp_csc_args(A);
 }
 
+// the checked copy of a caller's CSC with its CSR view
+template <typename real>
+void intake(DevCsc<real> &m, int N, int V, const pfdr_csc *A, int mem, hipStream_t s) {
+    HostPins pins(s);
+    m.take(N, V, A, mem, s, pins);
+    m.build_csr(s);
+    pins.release();
+}
+
 }  // namespace
 
-// pfdr_sparse_view.hpp: the entries' power method, also cut pursuit's on its
+// pfdr_spmat.hpp: the entries' power method, also cut pursuit's on its
 // sparse reduced operator
 template <typename real>
-real operator_norm_sparse(const SparseView<real> &A, real nTol, int itMax, int nbInit, int verbose,
+real operator_norm_sparse(const DevCsc<real> &A, real nTol, int itMax, int nbInit, int verbose,
                           hipStream_t s) {
     const long V = A.V, N = A.N;
     const int starts = std::max(nbInit, 1);
@@ -235,8 +243,8 @@ real operator_norm_sparse(const SparseView<real> &A, real nTol, int itMax, int n
             k_spn_scale<real><<<grid_for(V * B), kBlock, 0, s>>>(V, B, X.p, b.p);
         };
         auto step = [&]() {  // Y = A^t (A X)
-            apply<real>(B, N, A.rowptr, A.colidx, A.rval, X.p, T.p, s);
-            apply<real>(B, V, A.colptr, A.rowidx, A.val, T.p, Y.p, s);
+            apply<real>(B, N, A.rowptr.p, A.colidx.p, A.rval.p, X.p, T.p, s);
+            apply<real>(B, V, A.colptr.p, A.rowidx.p, A.val.p, T.p, Y.p, s);
         };
         // b = ||X||; X /= b; X = A^tA X; b = ||X|| (ref :193-196)
         col_norms<real>(V, B, X.p, part.p, b.p, s);
@@ -267,9 +275,9 @@ real operator_norm_sparse(const SparseView<real> &A, real nTol, int itMax, int n
     if (verbose) { printf("done.\n"); fflush(stdout); }
     return best;
 }
-template float operator_norm_sparse<float>(const SparseView<float> &, float, int, int, int,
+template float operator_norm_sparse<float>(const DevCsc<float> &, float, int, int, int,
                                            hipStream_t);
-template double operator_norm_sparse<double>(const SparseView<double> &, double, int, int, int,
+template double operator_norm_sparse<double>(const DevCsc<double> &, double, int, int, int,
                                              hipStream_t);
 
 namespace {
@@ -283,12 +291,12 @@ int opnorm_csc_host(const char *fn, int N, int V, const pfdr_csc *A, int mem, re
     // dense entry)
     try {
         hipStream_t s = lib_stream();
-        SparseView<real> view;
-        const std::shared_ptr<void> owner = sparse_view<real>(N, V, A, mem, s, view);
+        DevCsc<real> m;
+        intake(m, N, V, A, mem, s);
         const auto t0 = std::chrono::steady_clock::now();
-        *norm2 = operator_norm_sparse<real>(view, nTol, itMax, nbInit, verbose, s);
+        *norm2 = operator_norm_sparse<real>(m, nTol, itMax, nbInit, verbose, s);
         if (ms) {
-            ms[0] = view.csr_ms;
+            ms[0] = m.csr_ms;
             ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
                         .count();
         }
@@ -307,8 +315,8 @@ int lipschitz_csc_host(const char *fn, int N, int V, const pfdr_csc *A, int mem,
     if (!L) return report_error(fn, "L is NULL");
     try {
         hipStream_t s = lib_stream();
-        SparseView<real> view;
-        const std::shared_ptr<void> owner = sparse_view<real>(N, V, A, mem, s, view);
+        DevCsc<real> m;
+        intake(m, N, V, A, mem, s);
         DevBuf<double> r(N);
         DevBuf<real> buf;
         DevBuf<unsigned long long> mx(2);
@@ -318,8 +326,8 @@ int lipschitz_csc_host(const char *fn, int N, int V, const pfdr_csc *A, int mem,
             dL = buf.p;
         }
         PFDR_HIP(hipMemsetAsync(mx.p, 0, 2 * sizeof(unsigned long long), s));
-        k_spn_rowabs<real><<<grid_for(N), kBlock, 0, s>>>(N, view.rowptr, view.rval, r.p, mx.p);
-        k_spn_coldiag<real><<<grid_for(V), kBlock, 0, s>>>(V, view.colptr, view.rowidx, view.val,
+        k_spn_rowabs<real><<<grid_for(N), kBlock, 0, s>>>(N, m.rowptr.p, m.rval.p, r.p, mx.p);
+        k_spn_coldiag<real><<<grid_for(V), kBlock, 0, s>>>(V, m.colptr.p, m.rowidx.p, m.val.p,
                                                           r.p, dL, mx.p);
         PFDR_HIP(hipGetLastError());
         double h[2] = {0.0, 0.0};  // bit patterns of non-negative doubles
