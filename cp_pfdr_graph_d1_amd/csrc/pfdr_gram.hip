@@ -323,11 +323,13 @@ __global__ __launch_bounds__(64 * WG) void k_gram_v(int P, long K, const real *_
 // (up to ~2^-22 when the truncated leading piece leaves m near its bound;
 // tests/test_gram_split_cpu.py checks <= 2^-21), at the f32 rounding of the
 // sum.  A NaN in a tile (an overflow split into pieces of both signs, or an
-// infinite element) sends the whole Gram to the exact-f32 tile (gram()).  Six bf16 MFMAs of 16 k do the work of
-// eight f32 ones of 2 k at a sixteenth of the rate per flop: 2.7x the f32
-// matrix-core throughput.  Same blocks, tiles and chunks
-// as k_gram_v; the staging splits each element once, into three bf16
-// planes [row][k] (rows of BK + 8: 16-byte fragment reads conflict-free).
+// infinite element), or a non-zero element below 2^-109 (too small to split
+// exactly), sends the whole Gram to the exact-f32 tile (gram()).  Six bf16
+// MFMAs of 16 k do the work of eight f32 ones of 2 k at a sixteenth of the
+// rate per flop: 2.7x the f32 matrix-core throughput.
+// Same blocks, tiles and chunks as k_gram_v; the staging splits each element
+// once, into three bf16 planes [row][k] (rows of BK + 8: 16-byte fragment
+// reads conflict-free).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -435,7 +437,31 @@ __device__ __forceinline__ void gram_b_body(int P, long K, const float *__restri
             }
         }
     };
+    // The split is exact only down to 2^-110: bf16 subnormals end at 2^-133,
+    // and an element below 2^-110 has bits under that, which its l piece
+    // (and below 2^-118 its m piece) rounds away -- 2^-134 / |x| of each of
+    // its products, 2^-16 at 2^-118 and 2^-8 at 2^-126 (the matrix cores do
+    // keep subnormal bf16 inputs: tests/test_gram_exact_gpu.py
+    // test_tiny_against_huge_split).  A non-zero element below kSplitMin
+    // therefore raises the flag too, and gram() recomputes on the exact-f32
+    // tile, which keeps f32 subnormals.  Only the diagonal blocks look, at
+    // their side 0: between them they stage every element of A once.  Paired
+    // against the tile without it on one box: c3_ata's A^t A unchanged, C3's
+    // A A^t 16.6 -> 17.5 ms; looking in every block at both sides cost 8.5-
+    // 8.9 % of both, a pass of its own over A 9.4 % of C3's.
+    // (Flagged from the staging pass itself: a flag carried to the epilogue
+    // cost a register the tile does not have, 16-24 B of scratch per lane.)
+    constexpr unsigned kSplitMin = (127u - 109u) << 23;  // bits of 2^-109
+    auto tiny = [](float x) {  // 0 < |x| < 2^-109 (0 wraps to the top)
+        return (__builtin_bit_cast(unsigned, x) & 0x7fffffffu) - 1u < kSplitMin - 1u;
+    };
     auto store = [&]() {
+        if (bi == bj) {  // block-uniform
+            bool small = false;
+#pragma unroll
+            for (int q = 0; q < NK; q++) small |= tiny(st[0][q]);
+            if (small) nanflag[0] = 1;
+        }
         if (KI) {  // rows 2 rp, 2 rp + 1 at each of the lane's KQ k: 4 B per piece
             typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
             const int rp = t % (BT / RW), kq = (t / (BT / RW)) * KQ;
@@ -660,7 +686,7 @@ void gram(int which, int P, long K, const real *A, long ld, real *G, hipStream_t
         int h = 0;
         PFDR_HIP(hipMemcpyAsync(&h, nanflag.p, sizeof(int), hipMemcpyDeviceToHost, s));
         PFDR_HIP(hipStreamSynchronize(s));
-        if (h) {  // an overflow (or a non-finite input): the exact-f32 tile's semantics
+        if (h) {  // an overflow, a non-finite or a tiny input: the exact-f32 tile's semantics
             if (vec && which == 0)
                 k_gram_v<real, GRAM_TN><<<grid, 64 * kGramWaves, 0, s>>>(P, K, A, ld, kchunk,
                                                                         (int)nchunk, out);

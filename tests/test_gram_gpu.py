@@ -5,11 +5,17 @@ numpy and the reference's own power method (where built).
 Tolerances: the exact-f32 MFMA chain rounds once per product
 (≈1e-7 relative per element, cdna_hip_programming.md §3), so the f32 Gram
 is held to 2e-6 relative Frobenius error, f64 to 1e-13, and it must be
-exactly symmetric.  The power method stops on a relative evolution below
+exactly symmetric.  Beside the Frobenius norm every element (of a sub-block
+of Gram indices, where P x P x K is too much for a numpy reference) is held
+to the element-wise bars of tests/test_gram_exact_gpu.py: |G - ref| / (|A|^t
+|A|) within the derived 2 (K + chunks) u for f64, and for the split f32 tile
+within the plain f32 chain's own largest error on the same elements times
+gram_cases.SPLIT_MARGIN, plus 2^-21.  The power method stops on a relative evolution below
 nTol, so the squared norm is held to 10 nTol of the SVD value."""
 import numpy as np
 import pytest
 
+import gram_cases as gc
 from cp_pfdr_graph_d1_amd import pfdr
 
 pytestmark = pytest.mark.gpu
@@ -18,6 +24,23 @@ pytestmark = pytest.mark.gpu
 def _mat(M, N, seed, dt):
     rng = np.random.default_rng(seed)
     return rng.uniform(-1, 1, (M, N)).astype(dt)
+
+
+def _elementwise(G, A, which):
+    """largest |G - ref| / S over a sub-block of Gram indices, and its bar"""
+    P, K = (A.shape[1], A.shape[0]) if which == 0 else A.shape
+    f32 = A.dtype == np.float32
+    idx = gc.sample_indices(P, K, 4e8 if f32 else 5e7)    # (f64: a long double reference)
+    Gs, As = gc.sub_block(G, A, which, idx)
+    got = gc.normalised_error(Gs, As, which).max()
+    if f32:
+        chain = gc.normalised_error(gc.chain_f32(As, which), As, which).max()
+        bar = gc.split_bar(chain)
+    else:
+        bar = gc.length_bound(P, K, A.dtype)
+    u = gc.unit(A.dtype)
+    print("  element-wise over %d of %d indices: %.2f u (bar %.2f u)" % (idx.size, P, got / u, bar / u))
+    return got, bar
 
 
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
@@ -39,11 +62,15 @@ def test_gram_matches_numpy(gpu_lib, dt, shape, which):
     assert G.shape == ref.shape
     assert np.array_equal(G, G.T)
     assert err <= (2e-6 if dt == np.float32 else 1e-13)
+    got, bar = _elementwise(G, A, which)
+    assert got <= bar
 
 
 def test_gram_short_last_chunk(gpu_lib):
-    """A A^t of a 2048 x 20000 f32 A: 16 contraction chunks of 1280, the
-    last one 800 long (20000 = 15 x 1280 + 800)"""
+    """A A^t of a 2048 x 20000 f32 A: 32 contraction chunks of 640, the
+    last one 160 long (20000 = 31 x 640 + 160; gram() aims at 4096 blocks
+    of the split tile: 136 tiles x 31 -> 32 chunks)"""
+    assert (gc.plan(2048, 20000, np.float32)["nchunk"], gc.plan(2048, 20000, np.float32)["last"]) == (32, 160)
     A = _mat(2048, 20000, seed=7, dt=np.float32)
     G, ms = pfdr.gram(A, 1)
     A64 = A.astype(np.float64)
@@ -52,6 +79,8 @@ def test_gram_short_last_chunk(gpu_lib):
     print("gram 2048 x 20000 err=%.2e %.3f ms" % (err, ms))
     assert np.array_equal(G, G.T)
     assert err <= 2e-6
+    got, bar = _elementwise(G, A, 1)
+    assert got <= bar
 
 
 @pytest.mark.parametrize("which", [0, 1])
