@@ -22,6 +22,11 @@
 // through the direct branch: column norms, the equilibration round trip, the
 // CSC power method and L on the stored entries, the dense steps' bytes but
 // for c, which comes from another power method.
+// pfdr_cp_reduce_csc_sparse_preAt_* (cp_reduce_sparse_normal) keeps rA sparse
+// through the premultiplied branch: rAA and rY over the stored entries
+// (CpReduced::gram, ::dot) in the sequential Gram's order, at every size, and
+// the rest as above on rAA, so every byte is the dense branch's up to the 2^34
+// multiply-adds where that one leaves the reference's order.
 #include <cmath>
 #include <stdexcept>
 #include <string>
@@ -359,6 +364,93 @@ template long cp_reduce_sparse_direct<double>(CpCsc<double> &, int, const int *,
                                               double, int, int, CpReduced<double> &, double *,
                                               double *, hipStream_t);
 
+// The premultiplied branch above (:689-711, :776-800) with rAA and rY summed
+// over the stored entries of a sparse rA; from the mirror on, cp_reduce_host's
+// own launches.
+template <typename real>
+void cp_reduce_sparse_normal(CpCsc<real> &A, const real *Y, int rV, const int *rVc, const int *Vc,
+                             real normTol, int normItMax, int normNbInit, CpReduced<real> &rA,
+                             real *rAA, real *rY, real *l, real *L, hipStream_t s) {
+    A.reduced(rV, rVc, Vc, rA, s);
+    const int gy = rV < 65535 ? rV : 65535;
+    const dim3 b1(kBlock), gV(grid_for(rV)), gVV(grid_for(rV), gy);
+    rA.gram(rAA, s);
+    k_cp_mirror<real><<<gVV, b1, 0, s>>>(rV, rAA);
+    rA.dot(Y, rY, s);
+    k_cp_diag_sqrt<real><<<gV, b1, 0, s>>>(rV, rAA, l);
+    k_cp_scale_sym<real><<<gVV, b1, 0, s>>>(rV, rAA, l, 0);
+    PFDR_HIP(hipGetLastError());
+    const real c = operator_norm_device<real>(0, rV, rAA, normTol, normItMax, normNbInit, 0, s,
+                                              nullptr);
+    k_cp_scale_sym<real><<<gVV, b1, 0, s>>>(rV, rAA, l, 1);
+    if (L) k_cp_lipschitz<real><<<gV, b1, 0, s>>>(rV, l, c, L);
+    PFDR_HIP(hipGetLastError());
+    PFDR_HIP(hipStreamSynchronize(s));  // as cp_reduce_host: a session need not run on s
+}
+template void cp_reduce_sparse_normal<float>(CpCsc<float> &, const float *, int, const int *,
+                                             const int *, float, int, int, CpReduced<float> &,
+                                             float *, float *, float *, float *, hipStream_t);
+template void cp_reduce_sparse_normal<double>(CpCsc<double> &, const double *, int, const int *,
+                                              const int *, double, int, int, CpReduced<double> &,
+                                              double *, double *, double *, double *, hipStream_t);
+
+// the public entry of the premultiplied branch, rA returned as a CSC where asked for
+template <typename real>
+static int cp_reduce_csc_sparse_preAt(const char *fn, int N, int V, const pfdr_csc *A,
+                                      const real *Y, int rV, const int *rVc, const int *Vc,
+                                      int mem, real normTol, int normItMax, int normNbInit,
+                                      real *rAA, real *rY, real *L, real *Leq, int64_t *rnnz,
+                                      int64_t *rcolptr, int32_t *rrowidx, real *rval) {
+    if (N <= 0) return report_error(fn, "a sparse A needs N > 0");
+    if (V <= 0 || (mem != PFDR_MEM_HOST && mem != PFDR_MEM_DEVICE))
+        return report_error(fn, "invalid arguments");
+    if (const char *bad = cp_csc_args(A)) return report_error(fn, bad);
+    if (rV <= 0 || rV > V || !Y || !rVc || !Vc) return report_error(fn, "invalid arguments");
+    if (!rAA || !rY) return report_error(fn, "rAA and rY are required");
+    const int outs = (rnnz != nullptr) + (rcolptr != nullptr) + (rrowidx != nullptr) +
+                     (rval != nullptr);
+    if (outs != 0 && outs != 4)
+        return report_error(fn, "rnnz, rcolptr, rrowidx and rval must be all set or all NULL");
+    try {
+        hipStream_t s = lib_stream();
+        const bool dev = mem == PFDR_MEM_DEVICE;
+        CpCsc<real> sp;
+        sp.take(N, V, A, mem, s);
+        CpPartition part(rV, rVc, V, Vc, dev, s);
+        DevBuf<real> bY, brAA, brY, l(rV), dL(rV);
+        const real *dY = Y;
+        real *drAA = rAA, *drY = rY;
+        if (!dev) {
+            upload(bY, Y, (size_t)N, s);
+            brAA.alloc((size_t)rV * rV);
+            brY.alloc(rV);
+            dY = bY.p, drAA = brAA.p, drY = brY.p;
+        }
+        CpReduced<real> r;
+        cp_reduce_sparse_normal<real>(sp, dY, rV, part.rVc, part.Vc, normTol, normItMax,
+                                      normNbInit, r, drAA, drY, l.p, dL.p, s);
+        const auto k = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (!dev) {
+            PFDR_HIP(hipMemcpyAsync(rAA, drAA, (size_t)rV * rV * sizeof(real), k, s));
+            PFDR_HIP(hipMemcpyAsync(rY, drY, rV * sizeof(real), k, s));
+        }
+        if (rnnz) {
+            *rnnz = r.m.nnz;
+            PFDR_HIP(hipMemcpyAsync(rcolptr, r.m.colptr.p, ((size_t)rV + 1) * 8, k, s));
+            PFDR_HIP(hipMemcpyAsync(rrowidx, r.m.rowidx.p, (size_t)r.m.nnz * 4, k, s));
+            PFDR_HIP(hipMemcpyAsync(rval, r.m.val.p, (size_t)r.m.nnz * sizeof(real), k, s));
+        }
+        if (L) PFDR_HIP(hipMemcpyAsync(L, dL.p, rV * sizeof(real), k, s));
+        if (Leq) PFDR_HIP(hipMemcpyAsync(Leq, l.p, rV * sizeof(real), k, s));
+        PFDR_HIP(hipStreamSynchronize(s));
+    } catch (const HipError &h) {
+        return report_error(fn, h);
+    } catch (const std::exception &ex) {
+        return report_error(fn, ex.what());
+    }
+    return PFDR_OK;
+}
+
 // the public entry of the direct branch with rA returned as a CSC
 template <typename real>
 static int cp_reduce_csc_sparse(const char *fn, int N, int V, const pfdr_csc *A, const real *Y,
@@ -424,6 +516,23 @@ extern "C" int pfdr_cp_reduce_csc_sparse_f64(int N, int V, const pfdr_csc *A, co
     return pfdr::cp_reduce_csc_sparse<double>("pfdr_cp_reduce_csc_sparse_f64", N, V, A, Y, rV,
                                               rVc, Vc, mem, normTol, normItMax, normNbInit, rnnz,
                                               rcolptr, rrowidx, rval, L, Leq);
+}
+
+extern "C" int pfdr_cp_reduce_csc_sparse_preAt_f32(
+    int N, int V, const pfdr_csc *A, const float *Y, int rV, const int *rVc, const int *Vc, int mem,
+    float normTol, int normItMax, int normNbInit, float *rAA, float *rY, float *L, float *Leq,
+    int64_t *rnnz, int64_t *rcolptr, int32_t *rrowidx, float *rval) {
+    return pfdr::cp_reduce_csc_sparse_preAt<float>(
+        "pfdr_cp_reduce_csc_sparse_preAt_f32", N, V, A, Y, rV, rVc, Vc, mem, normTol, normItMax,
+        normNbInit, rAA, rY, L, Leq, rnnz, rcolptr, rrowidx, rval);
+}
+extern "C" int pfdr_cp_reduce_csc_sparse_preAt_f64(
+    int N, int V, const pfdr_csc *A, const double *Y, int rV, const int *rVc, const int *Vc,
+    int mem, double normTol, int normItMax, int normNbInit, double *rAA, double *rY, double *L,
+    double *Leq, int64_t *rnnz, int64_t *rcolptr, int32_t *rrowidx, double *rval) {
+    return pfdr::cp_reduce_csc_sparse_preAt<double>(
+        "pfdr_cp_reduce_csc_sparse_preAt_f64", N, V, A, Y, rV, rVc, Vc, mem, normTol, normItMax,
+        normNbInit, rAA, rY, L, Leq, rnnz, rcolptr, rrowidx, rval);
 }
 
 extern "C" int pfdr_cp_reduce_csc_f32(int N, int V, const pfdr_csc *A, const float *Y, int rV,

@@ -82,6 +82,10 @@ struct CpDriverBase {
     // iterations solved on a dense one, the most entries a sparse rA stored.
     int reduced = PFDR_REDUCED_DENSE;
     int64_t sparse_its = 0, dense_direct_its = 0, max_rnnz = 0;
+    // The same of the premultiplied iterations (N > 0), which only
+    // PFDR_REDUCED_SPARSE_ALL solves from stored entries
+    // (pfdr_cp_solver_premultiplied_stats).
+    int64_t pre_sparse_its = 0, pre_dense_its = 0, pre_max_rnnz = 0;
     virtual bool holds_sparse_A() const { return false; }
 
     // p.mem = PFDR_MEM_DEVICE: the arrays are device memory, copied except A,

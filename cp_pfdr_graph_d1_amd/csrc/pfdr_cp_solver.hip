@@ -492,9 +492,20 @@ extern "C" int pfdr_cp_solver_set_reduced(pfdr_cp_solver *h, int mode) {
         return report_error(fn, "the simplex kind has no reduced operator");
     if (!h->d->holds_sparse_A())
         return report_error(fn, "the solver was not created by pfdr_cp_solver_create_sparse");
-    if (mode != PFDR_REDUCED_DENSE && mode != PFDR_REDUCED_SPARSE)
-        return report_error(fn, "mode must be PFDR_REDUCED_DENSE or PFDR_REDUCED_SPARSE");
+    if (mode != PFDR_REDUCED_DENSE && mode != PFDR_REDUCED_SPARSE &&
+        mode != PFDR_REDUCED_SPARSE_ALL)
+        return report_error(fn, "mode must be PFDR_REDUCED_DENSE, PFDR_REDUCED_SPARSE or "
+                                "PFDR_REDUCED_SPARSE_ALL");
     h->d->reduced = mode;
+    return PFDR_OK;
+}
+
+extern "C" int pfdr_cp_solver_premultiplied_stats(pfdr_cp_solver *h, int64_t *sparse_iterations,
+                                                  int64_t *dense_iterations, int64_t *max_rnnz) {
+    if (!h) return report_error("pfdr_cp_solver_premultiplied_stats", "invalid arguments");
+    if (sparse_iterations) *sparse_iterations = h->d->pre_sparse_its;
+    if (dense_iterations) *dense_iterations = h->d->pre_dense_its;
+    if (max_rnnz) *max_rnnz = h->d->pre_max_rnnz;
     return PFDR_OK;
 }
 

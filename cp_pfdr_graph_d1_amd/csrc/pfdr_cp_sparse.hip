@@ -28,6 +28,14 @@
 // the dense kernels' order (k_cp_colnorm, k_cp_scale_cols, k_cpq_residual).
 //
 // Gradient: one lane per column, products formed, then added in stored order.
+//
+// The reduced normal equations of a premultiplied iteration (CpReduced::gram,
+// ::dot): rAA = rA^t rA and rY = rA^t Y over the stored entries, in the order
+// of k_cp_gram_seq and k_cp_rY_dot (pfdr_cp.hip) and so with their bytes; the
+// Gram kernel densifies one column at a time in a window of LDS and is
+// described at k_cpsp_gram.
+#include <cstdlib>
+
 #include "pfdr_cp_sparse.hpp"
 #include "pfdr_sort.hpp"
 
@@ -332,14 +340,106 @@ __global__ __launch_bounds__(256) void k_cpsp_residual(int N, const int64_t *__r
     R[n] = Y[n] - a;
 }
 
-// DfS[v] = -(sum of val[e] R[rowidx[e]]), column v's entries in stored order;
-// 4 entries' loads in flight ahead of the adds
+// ---- rAA = rA^t rA over the stored entries (CpReduced::gram)
+// The window of rows that one workgroup holds densified in LDS: 32 KiB, so
+// that five workgroups fit a CU's 160 KiB.
+constexpr int kGramLdsBytes = 32 * 1024;
+
+// the first e in [lo, hi) with rowidx[e] >= row (hi where there is none)
+__device__ __forceinline__ int64_t cpsp_lower(const int *__restrict__ rowidx, int64_t lo,
+                                              int64_t hi, long row) {
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (rowidx[mid] < row) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Upper triangle rAA[rv + rV ru], rv <= ru: the products of the rows stored in
+// both columns, rows ascending, each product formed and then added from +0
+// (k_cp_gram_seq without its +-0 terms).  One workgroup per column ru, the
+// longest triangle columns first.  It walks ru's row range in windows of W
+// rows: the window is zeroed in LDS and ru's entries in it are scattered in;
+// then lane t takes rv = t, t + 256, ... <= ru and adds val * win[row - base]
+// over column rv's entries in the window, found by binary search, 4 entries'
+// loads ahead of the adds.  Where ru stores nothing the factor is the window's
+// +0, the dense loop's own term.  A pair's sum is carried from window to
+// window in rAA itself, written and read back by the same lane; a window in
+// which ru stores nothing is skipped, and so is a column rv that stores
+// nothing in a later window.  No atomics.
 template <typename real>
-__global__ __launch_bounds__(256) void k_cpsp_grad(int V, const int64_t *__restrict__ colptr,
+__global__ __launch_bounds__(256) void k_cpsp_gram(int rV, int W,
+                                                   const int64_t *__restrict__ colptr,
                                                    const int *__restrict__ rowidx,
                                                    const real *__restrict__ val,
-                                                   const real *__restrict__ R,
-                                                   real *__restrict__ DfS) {
+                                                   real *__restrict__ rAA) {
+    __shared__ real win[kGramLdsBytes / sizeof(real)];
+    const int ru = rV - 1 - (int)blockIdx.x;
+    const int64_t u0 = colptr[ru], u1 = colptr[ru + 1];
+    real *out = rAA + (size_t)rV * ru;
+    if (u0 == u1) {  // an empty column: no common row with any
+        for (long rv = threadIdx.x; rv <= ru; rv += kBlock) out[rv] = real(0);
+        return;
+    }
+    const long first = rowidx[u0], last = rowidx[u1 - 1];
+    bool fresh = true;  // no window has written the sums yet
+    int64_t ua = u0;    // ru's first entry at or after the window
+    for (long base = first; base <= last; base += W) {
+        const long lim = base + W;
+        const int64_t ub = cpsp_lower(rowidx, ua, u1, lim);
+        if (ub == ua) continue;  // (never the first window: it holds row `first`)
+        for (int i = threadIdx.x; i < W; i += kBlock) win[i] = real(0);
+        __syncthreads();
+        for (int64_t e = ua + threadIdx.x; e < ub; e += kBlock) win[rowidx[e] - base] = val[e];
+        __syncthreads();
+        for (long rv = threadIdx.x; rv <= ru; rv += kBlock) {
+            const int64_t e1 = colptr[rv + 1];
+            int64_t e = cpsp_lower(rowidx, colptr[rv], e1, base);
+            if (!fresh && (e == e1 || rowidx[e] >= lim)) continue;
+            real s = fresh ? real(0) : out[rv];
+            constexpr int U = 4;
+            for (; e + U <= e1; e += U) {
+                int r[U];
+                real x[U], y[U];
+#pragma unroll
+                for (int q = 0; q < U; q++) {
+                    r[q] = rowidx[e + q];
+                    x[q] = val[e + q];
+                }
+                if (r[U - 1] >= lim) break;  // the window ends inside these: one by one below
+#pragma unroll
+                for (int q = 0; q < U; q++) y[q] = win[r[q] - base];
+#pragma unroll
+                for (int q = 0; q < U; q++) {
+                    const real b = x[q] * y[q];
+                    s += b;
+                }
+            }
+            for (; e < e1; e++) {
+                const long r = rowidx[e];
+                if (r >= lim) break;
+                const real b = val[e] * win[r - base];
+                s += b;
+            }
+            out[rv] = s;
+        }
+        fresh = false;
+        ua = ub;
+        __syncthreads();  // the window is zeroed again
+    }
+}
+
+// out[v] = the sum of val[e] w[rowidx[e]] over column v's entries in stored
+// order, each product formed and then added from +0 (NEG: its negative); 4
+// entries' loads in flight ahead of the adds.  The gradient DfS = -A^t R and
+// rY = rA^t Y (k_cp_rY_dot without its +-0 terms).
+template <typename real, bool NEG>
+__global__ __launch_bounds__(256) void k_cpsp_coldot(int V, const int64_t *__restrict__ colptr,
+                                                     const int *__restrict__ rowidx,
+                                                     const real *__restrict__ val,
+                                                     const real *__restrict__ R,
+                                                     real *__restrict__ DfS) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
     int64_t e = colptr[v];
@@ -363,7 +463,7 @@ __global__ __launch_bounds__(256) void k_cpsp_grad(int V, const int64_t *__restr
         const real b = val[e] * R[rowidx[e]];
         s += b;
     }
-    DfS[v] = -s;
+    DfS[v] = NEG ? -s : s;
 }
 
 }  // namespace
@@ -466,8 +566,34 @@ void CpReduced<real>::residual(const real *rX, const real *Y, real *R, hipStream
 
 template <typename real>
 void CpCsc<real>::gradient(const real *R, real *DfS, hipStream_t s) const {
-    k_cpsp_grad<real><<<grid_for(m.V), kBlock, 0, s>>>(m.V, m.colptr.p, m.rowidx.p, m.val.p, R,
-                                                       DfS);
+    k_cpsp_coldot<real, true><<<grid_for(m.V), kBlock, 0, s>>>(m.V, m.colptr.p, m.rowidx.p,
+                                                               m.val.p, R, DfS);
+    PFDR_HIP(hipGetLastError());
+}
+
+// The rows of k_cpsp_gram's window: as many as its LDS holds (cap), or
+// PFDR_CP_GRAM_WINDOW where that is a whole number in [1, cap); read at every
+// call, so a test may change it between two calls of one process.
+static int cp_gram_window(int cap) {
+    if (const char *e = std::getenv("PFDR_CP_GRAM_WINDOW")) {
+        char *end = nullptr;
+        const long w = std::strtol(e, &end, 10);
+        if (end != e && *end == 0 && w >= 1 && w < cap) return (int)w;
+    }
+    return cap;
+}
+
+template <typename real>
+void CpReduced<real>::gram(real *rAA, hipStream_t s) const {
+    const int W = cp_gram_window(kGramLdsBytes / (int)sizeof(real));
+    k_cpsp_gram<real><<<m.V, kBlock, 0, s>>>(m.V, W, m.colptr.p, m.rowidx.p, m.val.p, rAA);
+    PFDR_HIP(hipGetLastError());
+}
+
+template <typename real>
+void CpReduced<real>::dot(const real *Y, real *rY, hipStream_t s) const {
+    k_cpsp_coldot<real, false><<<grid_for(m.V), kBlock, 0, s>>>(m.V, m.colptr.p, m.rowidx.p,
+                                                                m.val.p, Y, rY);
     PFDR_HIP(hipGetLastError());
 }
 

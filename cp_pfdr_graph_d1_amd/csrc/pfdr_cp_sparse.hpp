@@ -4,7 +4,9 @@
 //   colsum    the component column sums rA (N-by-rV, dense) of pfdr_cp_reduce
 //             and of the drivers' initialize() (one component, Vc = identity)
 //   reduced   the same sums kept sparse: rA as a CSC with its CSR view
-//             (CpReduced), for the direct branch of pfdr_cp_reduce
+//             (CpReduced), for the direct branch of pfdr_cp_reduce and, with
+//             rAA = rA^t rA and rY = rA^t Y over its entries (gram, dot), for
+//             the premultiplied one
 //   gradient  DfS = -A^t R, the base of pfdr_cpgraph_gradient for N > 0
 //   take      the copy and the structural checks of a caller's pfdr_csc
 //             (DevCsc, pfdr_spmat.hpp)
@@ -37,6 +39,18 @@ struct CpReduced {
     // R[n] = Y[n] - (sum of rval * rX[colidx] over row n's entries, rv
     // ascending, from +0): k_cpq_residual's bytes on the densified rA
     void residual(const real *rX, const real *Y, real *R, hipStream_t s) const;
+    // Upper triangle rAA[rv + rV ru], rv <= ru (device, rV^2; the rest is left
+    // alone): the products over the rows stored in both columns, rows
+    // ascending, each formed and then added from +0; +0 where there is none.
+    // k_cp_gram_seq's bytes on the densified rA, at every size (the dense
+    // entry goes to the matrix cores above 2^34 products and agrees with this
+    // one to that Gram's tolerance only there: this is the one in the
+    // reference's order).  No atomics; no scratch beyond a window of LDS,
+    // whose rows PFDR_CP_GRAM_WINDOW overrides (read at every call).
+    void gram(real *rAA, hipStream_t s) const;
+    // rY[rv] = the sum of val * Y[row] over column rv's entries, rows
+    // ascending, from +0: k_cp_rY_dot's bytes
+    void dot(const real *Y, real *rY, hipStream_t s) const;
     pfdr_csc csc() const { return pfdr_csc{m.nnz, m.colptr.p, m.rowidx.p, m.val.p}; }
 };
 
@@ -94,6 +108,19 @@ template <typename real>
 long cp_reduce_sparse_direct(CpCsc<real> &A, int rV, const int *rVc, const int *Vc, real normTol,
                              int normItMax, int normNbInit, CpReduced<real> &rA, real *l, real *L,
                              hipStream_t s);
+
+// The premultiplied branch (preAt = 1, N > 0) of pfdr_cp_reduce_* on the stored
+// entries (pfdr_cp.hip): rA as a CpReduced (not scaled, as the dense branch
+// leaves its rA), rAA = rA^t rA (device, rV^2, mirrored) and rY = rA^t Y by
+// CpReduced::gram and ::dot, then the dense branch's own launches on rAA: l =
+// the roots of its diagonal (device, rV), the equilibration round trip around
+// operator_norm_device, and L = l (l c) (device, rV, or nullptr).  Every output
+// has the dense branch's bytes while its Gram is the sequential one (see
+// CpReduced::gram).  Synchronises.
+template <typename real>
+void cp_reduce_sparse_normal(CpCsc<real> &A, const real *Y, int rV, const int *rVc, const int *Vc,
+                             real normTol, int normItMax, int normNbInit, CpReduced<real> &rA,
+                             real *rAA, real *rY, real *l, real *L, hipStream_t s);
 
 // pfdr_cpgraph_gradient (pfdr_cpgraph.hip) for N > 0 with the base taken from
 // A, a CpCsc of the graph's real type; R on the device, DfS stays there.

@@ -304,7 +304,7 @@ struct QuadDriver : CpDriverBase {
     void residual_from_state() {
         CP_ABI(pfdr_cpgraph_get_components(g, nullptr, nullptr, dVc.p, drVc.p, PFDR_MEM_DEVICE));
         DevBuf<real> L(rV);
-        if (reduced == PFDR_REDUCED_SPARSE) {
+        if (reduced != PFDR_REDUCED_DENSE) {
             // the same sums over the stored entries, through the equilibration's
             // divide and multiply (no norm: R does not read L); a column of
             // norm 0 takes the dense branch, as in the loop
@@ -358,6 +358,7 @@ struct QuadDriver : CpDriverBase {
         auto t = t0;
         st = CpStats{};
         sparse_its = dense_direct_its = max_rnnz = 0;
+        pre_sparse_its = pre_dense_its = pre_max_rnnz = 0;
         const bool bounds = flavour == Flavour::Bounds;
         // flavour: the two-layer cut (duplex :469-545); else one cut when nothing
         // but the d1 term bends the functional (bounds :392), or two
@@ -473,13 +474,22 @@ struct QuadDriver : CpDriverBase {
             DevBuf<real> rA, rAAd, rYd, L(rV);
             // a direct iteration of the sparse mode keeps rA sparse, unless a
             // reduced column has norm 0 (a sparse session refuses it): then,
-            // and in every other case, the dense rA
+            // and in every other case, the dense rA -- but for a premultiplied
+            // iteration (N > 0) of PFDR_REDUCED_SPARSE_ALL, which keeps rA
+            // sparse too and sums rAA and rY over its entries
             CpReduced<real> rs;
             bool sparse_rA = false;
-            if (!preAt && reduced == PFDR_REDUCED_SPARSE) {
+            if (!preAt && reduced != PFDR_REDUCED_DENSE) {
                 DevBuf<real> l(rV);
                 sparse_rA = cp_reduce_sparse_direct<real>(sp, rV, drVc.p, dVc.p, real(1e-3), 100,
                                                           10, rs, l.p, L.p, s) < 0;
+            } else if (preAt && N > 0 && reduced == PFDR_REDUCED_SPARSE_ALL) {
+                DevBuf<real> l(rV);
+                rYd.alloc(rV);
+                rAAd.alloc((size_t)rV * rV);
+                cp_reduce_sparse_normal<real>(sp, dY.p, rV, drVc.p, dVc.p, real(1e-3), 100, 10, rs,
+                                              rAAd.p, rYd.p, l.p, L.p, s);
+                sparse_rA = true;
             }
             if (!sparse_rA) {
                 if (N > 0) rA.alloc((size_t)N * rV);
@@ -489,7 +499,14 @@ struct QuadDriver : CpDriverBase {
                 }
                 reduce(preAt, rA.p, rAAd.p, rYd.p, L.p);
             }
-            if (sparse_rA) {
+            if (preAt && N > 0) {
+                if (sparse_rA) {
+                    pre_sparse_its++;
+                    if (rs.m.nnz > pre_max_rnnz) pre_max_rnnz = rs.m.nnz;
+                } else {
+                    pre_dense_its++;
+                }
+            } else if (sparse_rA) {
                 sparse_its++;
                 if (rs.m.nnz > max_rnnz) max_rnnz = rs.m.nnz;
             } else if (!preAt) {
@@ -527,8 +544,10 @@ struct QuadDriver : CpDriverBase {
                 p.difTol = (real)q.difTol;
                 p.itMax = q.itMax;
                 p.verbose = verbose;
-                if (sparse_rA) pit = cp_pfdr_solve_sparse(p, rs.csc(), sizeof(real) * rV, s);
-                else pit = cp_pfdr_solve(p, sizeof(real) * rV, s);
+                if (sparse_rA && !preAt)
+                    pit = cp_pfdr_solve_sparse(p, rs.csc(), sizeof(real) * rV, s);
+                else
+                    pit = cp_pfdr_solve(p, sizeof(real) * rV, s);
             }
             st.pfdr += since(t);
             st.pfdr_it += pit;

@@ -26,7 +26,7 @@ PFDR_F32, PFDR_F64 = 0, 1
 PFDR_MEM_HOST, PFDR_MEM_DEVICE = 0, 1
 PFDR_KIND_L1, PFDR_KIND_BOUNDS, PFDR_KIND_SIMPLEX = 0, 1, 2
 SCAL, DIAG = 0, 1
-PFDR_REDUCED_DENSE, PFDR_REDUCED_SPARSE = 0, 1
+PFDR_REDUCED_DENSE, PFDR_REDUCED_SPARSE, PFDR_REDUCED_SPARSE_ALL = 0, 1, 2
 REORDER_AUTO, REORDER_ON, REORDER_OFF = 0, 1, 2
 # iterate-evolution statistic (include/pfdr_mi355x.h PFDR_EVOLUTION_*)
 EVOLUTION_AUTO, EVOLUTION_SEQUENTIAL, EVOLUTION_TREE = 0, 1, 2
@@ -76,6 +76,7 @@ EXPORTED = (
     "pfdr_cp_solver_get_state", "pfdr_cp_solver_set_state", "pfdr_cp_solver_set_partition",
     "pfdr_cp_solver_set_penalties", "pfdr_cp_solver_stats",
     "pfdr_cp_solver_set_reduced", "pfdr_cp_solver_reduced_stats",
+    "pfdr_cp_solver_premultiplied_stats",
     "pfdr_cpgraph_set_weights", "pfdr_cpgraph_set_active_by_labels",
     "pfdr_session_create", "pfdr_session_run", "pfdr_session_prepare", "pfdr_session_result",
     "pfdr_session_device_x", "pfdr_session_set_profiling", "pfdr_session_profile_filter",
@@ -97,6 +98,9 @@ EXPORTED = (
     "pfdr_gen_matvec_f64", "pfdr_gen_symmetric_f32", "pfdr_gen_symmetric_f64",
     "pfdr_locality_order",
 )
+# the entries named after the reference's preAt, the header's only names with a
+# capital letter: declared there and required of the library like the above
+EXPORTED_PREAT = ("pfdr_cp_reduce_csc_sparse_preAt_f32", "pfdr_cp_reduce_csc_sparse_preAt_f64")
 
 
 class PFDRError(RuntimeError):
@@ -187,6 +191,8 @@ def _solver_argtypes(lib, vp):
     if hasattr(lib, "pfdr_cp_solver_set_reduced"):
         lib.pfdr_cp_solver_set_reduced.argtypes = [vp, C.c_int]
         lib.pfdr_cp_solver_reduced_stats.argtypes = [vp, vp, vp, vp]
+    if hasattr(lib, "pfdr_cp_solver_premultiplied_stats"):
+        lib.pfdr_cp_solver_premultiplied_stats.argtypes = [vp, vp, vp, vp]
 
 
 def load():
@@ -585,6 +591,15 @@ class Lib:
                "pfdr_cp_solver_reduced_stats")
         return tuple(int(x) for x in out)
 
+    def cp_solver_premultiplied_stats(self, handle):
+        """-> (iterations solved from stored entries, iterations that formed a
+        dense rA, max rnnz) of the last run's premultiplied iterations, N > 0"""
+        out = np.zeros(3, np.int64)
+        a = out.ctypes.data
+        _check(self.lib.pfdr_cp_solver_premultiplied_stats(handle, a, a + 8, a + 16),
+               "pfdr_cp_solver_premultiplied_stats")
+        return tuple(int(x) for x in out)
+
     def cp_loss_d1_simplex_stats(self, n_exp=64):
         """pfdr_cp_loss_d1_simplex_stats of this thread's last cp_loss_d1_simplex
         -> dict: seconds per phase, counts, rounds / relabels per expansion"""
@@ -844,7 +859,7 @@ def _cp_front(flavour, V, N, Y, A, Eu, Ev, La_d1, own, CP_difTol, CP_itMax, rho,
     if isinstance(A, CSC):
         call, kw = _cp_sparse_run, dict(reduced=reduced)
     elif _reduced_mode(reduced) != PFDR_REDUCED_DENSE:
-        raise ValueError('reduced="sparse" needs A as a CSC')
+        raise ValueError('reduced="%s" needs A as a CSC' % (reduced,))
     Cv, rX, it, Obj, Dif, Time = call(
         flavour, V, N, Y, A, Eu, Ev, np.asarray(La_d1, Y.dtype), own, CP_difTol, CP_itMax, rho,
         condMin, difRcd, difTol, itMax, verbose, **kw)
@@ -871,7 +886,8 @@ def CP_PFDR_graph_quadratic_d1_bounds(Y, A, Eu, Ev, La_d1, Bnd, CP_difTol, CP_it
     (pfdr_cp_quadratic_d1_bounds).  Returns (Cv, rX, CP_it, Time, Obj, Dif): the
     component of every vertex (int32[V]), the value of every component -- the
     minimiser is rX[Cv] -- and the records asked for (None otherwise).
-    reduced="sparse" (a CSC A only): CPSolver's sparse reduced operator."""
+    reduced="sparse" / "sparse_all" (a CSC A only): CPSolver's sparse reduced
+    operator."""
     dt = np.result_type(Y, np.float32)
     A, (N, V) = _cp_matrix(A, dt)
     return _cp_front("bounds", V, N, np.asarray(Y, dt).ravel(), A, Eu, Ev, La_d1, Bnd, CP_difTol,
@@ -917,8 +933,8 @@ def CP_PFDR_graph_quadratic_d1_l1_duplex(Y, A, Eu, Ev, La_d1, La_l1, positivity,
     the whole loop on the GPU (pfdr_cp_quadratic_d1_l1_duplex).  La_l1: array,
     scalar or None.  Returns (Cv, rX, CP_it, Time, Obj, Dif): the component of every vertex
     (int32[V]), the value of every component -- the minimiser is rX[Cv] -- and
-    the records asked for (None otherwise).  reduced="sparse" (a CSC A only):
-    CPSolver's sparse reduced operator."""
+    the records asked for (None otherwise).  reduced="sparse" / "sparse_all" (a
+    CSC A only): CPSolver's sparse reduced operator."""
     dt = np.result_type(Y, np.float32)
     A, (N, V) = _cp_matrix(A, dt)
     return _cp_front("duplex", V, N, np.asarray(Y, dt).ravel(), A, Eu, Ev, La_d1,
@@ -1052,7 +1068,7 @@ def _cp_binding(flavour, reduced, obs, source, target, edge_weight, A, l1_weight
                            reduced=reduced)
         return r[0].astype(np.uint32), r[1]
     if _reduced_mode(reduced) != PFDR_REDUCED_DENSE:
-        raise ValueError('reduced="sparse" needs A as a CSC')
+        raise ValueError('reduced="%s" needs A as a CSC' % (reduced,))
     if mode == "identity":
         N, A = 0, None
     elif mode == "diagonal":
@@ -1074,7 +1090,8 @@ def CP_quadratic_l1(obs, source, target, edge_weight, A, l1_weight, positivity=0
     (pfdr_cp_quadratic_d1_l1).  Returns (Cv, rX): the component of every
     vertex (uint32, as the binding) and the value of every component.
     reduced="sparse" (a CSC A only): CPSolver's sparse reduced operator, which
-    agrees with the default to the solvers' tolerances, not to the byte."""
+    agrees with the default to the solvers' tolerances, not to the byte;
+    reduced="sparse_all": the premultiplied iterations on stored entries too."""
     return _cp_binding("l1", reduced, obs, source, target, edge_weight, A, l1_weight, positivity,
                        CP_difTol, CP_itMax, PFDR_rho, PFDR_condMin, PFDR_difRcd, PFDR_difTol,
                        PFDR_itMax, verbose)
@@ -1476,12 +1493,14 @@ def lipschitz_diag(csc):
 
 
 def _reduced_mode(reduced):
-    """"dense" / "sparse" -> PFDR_REDUCED_*; an integer as it is (the library
-    refuses the ones it does not know)"""
-    modes = {"dense": PFDR_REDUCED_DENSE, "sparse": PFDR_REDUCED_SPARSE}
+    """"dense" / "sparse" / "sparse_all" -> PFDR_REDUCED_*; an integer as it is
+    (the library refuses the ones it does not know)"""
+    modes = {"dense": PFDR_REDUCED_DENSE, "sparse": PFDR_REDUCED_SPARSE,
+             "sparse_all": PFDR_REDUCED_SPARSE_ALL}
     if isinstance(reduced, str):
         if reduced not in modes:
-            raise ValueError('reduced must be "dense" or "sparse", got %r' % (reduced,))
+            raise ValueError('reduced must be "dense", "sparse" or "sparse_all", got %r' % (
+                reduced,))
         return modes[reduced]
     return int(reduced)
 
@@ -1494,7 +1513,10 @@ def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normIt
     goes through pfdr_cp_reduce_csc_* and gives the bytes of its densified
     matrix.  Returns dict rA, rAA, rY, L, Leq (None where not formed).
     reduced="sparse" (a CSC A, preAt=False): pfdr_cp_reduce_csc_sparse_*, "rA"
-    is a host CSC (N-by-rV) that is never densified, rAA and rY are None."""
+    is a host CSC (N-by-rV) that is never densified, rAA and rY are None.
+    reduced="sparse_all" (a CSC A): the same for preAt=False, and for
+    preAt=True pfdr_cp_reduce_csc_sparse_preAt_*: "rA" is that CSC (not
+    scaled), rAA and rY are summed over its stored entries."""
     Y = np.asarray(Y)
     dt = Y.dtype
     ct, sfx, _ = _real(dt)
@@ -1504,12 +1526,13 @@ def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normIt
     Af = None
     sparse = isinstance(A, CSC)
     mode = _reduced_mode(reduced)
-    if mode not in (PFDR_REDUCED_DENSE, PFDR_REDUCED_SPARSE):
-        raise ValueError('cp_reduce: reduced must be "dense" or "sparse", got %r' % (reduced,))
-    if mode == PFDR_REDUCED_SPARSE:
+    if mode not in (PFDR_REDUCED_DENSE, PFDR_REDUCED_SPARSE, PFDR_REDUCED_SPARSE_ALL):
+        raise ValueError('cp_reduce: reduced must be "dense", "sparse" or "sparse_all", got %r'
+                         % (reduced,))
+    if mode != PFDR_REDUCED_DENSE:
         if not sparse:
-            raise ValueError('cp_reduce: reduced="sparse" needs A as a CSC')
-        if preAt:
+            raise ValueError('cp_reduce: reduced="%s" needs A as a CSC' % (reduced,))
+        if preAt and mode == PFDR_REDUCED_SPARSE:
             raise ValueError('cp_reduce: reduced="sparse" is the direct branch, preAt=False')
         A = A.to_host().astype(dt)
         csc = A.struct()
@@ -1518,14 +1541,21 @@ def cp_reduce(N, A, Y, comp_ptr, comp_vertices, preAt=True, normTol=1e-3, normIt
         rcolptr = np.zeros(rV + 1, np.int64)
         rrowidx, rval = np.zeros(A.nnz, np.int32), np.zeros(A.nnz, dt)
         L, Leq = np.zeros(rV, dt), np.zeros(rV, dt)
+        rAA = rY = None
         p = lambda a: C.c_void_p(a.ctypes.data)
-        _check(getattr(load(), "pfdr_cp_reduce_csc_sparse_" + sfx)(
-            C.c_int(N), C.c_int(V), C.byref(csc), p(Yc), C.c_int(rV), p(ptr), p(Vc),
-            PFDR_MEM_HOST, ct(normTol), C.c_int(normItMax), C.c_int(normNbInit), C.byref(rnnz),
-            p(rcolptr), p(rrowidx), p(rval), p(L), p(Leq)), "pfdr_cp_reduce_csc_sparse")
+        head = (C.c_int(N), C.c_int(V), C.byref(csc), p(Yc), C.c_int(rV), p(ptr), p(Vc),
+                PFDR_MEM_HOST, ct(normTol), C.c_int(normItMax), C.c_int(normNbInit))
+        kept = (C.byref(rnnz), p(rcolptr), p(rrowidx), p(rval))
+        if preAt:
+            rAA, rY = np.zeros((rV, rV), dt), np.zeros(rV, dt)
+            _check(getattr(load(), "pfdr_cp_reduce_csc_sparse_preAt_" + sfx)(
+                *head, p(rAA), p(rY), p(L), p(Leq), *kept), "pfdr_cp_reduce_csc_sparse_preAt")
+        else:
+            _check(getattr(load(), "pfdr_cp_reduce_csc_sparse_" + sfx)(
+                *head, *kept, p(L), p(Leq)), "pfdr_cp_reduce_csc_sparse")
         n = rnnz.value
-        return {"rA": CSC(rcolptr, rrowidx[:n].copy(), rval[:n].copy(), N), "rAA": None,
-                "rY": None, "L": L, "Leq": Leq}
+        return {"rA": CSC(rcolptr, rrowidx[:n].copy(), rval[:n].copy(), N), "rAA": rAA,
+                "rY": rY, "L": L, "Leq": Leq}
     if sparse:
         A = A.to_host().astype(dt)
         csc = A.struct()
@@ -1811,7 +1841,7 @@ class CPGraph:
 
 
 class _CPSolverType(type):
-    """CPSolver(..., reduced="dense" | "sparse"): the keyword is no argument of
+    """CPSolver(..., reduced="dense" | "sparse" | "sparse_all"): the keyword is no argument of
     the constructor proper but a set_reduced() on the finished solver, which
     the library refuses (PFDRError) unless A came as a CSC"""
 
@@ -1842,7 +1872,9 @@ class CPSolver(metaclass=_CPSolverType):
     reduced="sparse" (or set_reduced) keeps the reduced operator of a direct
     iteration sparse as well (pfdr_cp_solver_set_reduced): the dense N-by-rV
     array is never allocated there, and a run then agrees with the default to the
-    solvers' tolerances.  The first run() equals the matching
+    solvers' tolerances; reduced="sparse_all" also sums the normal equations of
+    a premultiplied iteration over the stored entries of a sparse rA, with the
+    default's bytes (premultiplied_stats() counts them).  The first run() equals the matching
     Lib.cp_* call byte for byte; every later one is the reference's warm restart
     from the state the handle holds."""
 
@@ -2005,15 +2037,22 @@ class CPSolver(metaclass=_CPSolverType):
                                         PFDR_MEM_DEVICE if dev else PFDR_MEM_HOST)
 
     def set_reduced(self, reduced):
-        """"dense" or "sparse" (pfdr_cp_solver_set_reduced): how the reduced
-        operator of a direct iteration is kept; a solver with a CSC A only.
-        The state is kept."""
+        """"dense", "sparse" or "sparse_all" (pfdr_cp_solver_set_reduced): how
+        the reduced operator of a direct iteration ("sparse") and of a
+        premultiplied one as well ("sparse_all") is kept; a solver with a CSC A
+        only.  The state is kept."""
         self._L.cp_solver_set_reduced(self._h, _reduced_mode(reduced))
 
     def reduced_stats(self):
-        """-> (iterations solved on a sparse rA, direct iterations solved on a
-        dense one, the most entries a sparse rA held) of the last run"""
+        """-> (direct iterations solved on a sparse rA, direct iterations solved
+        on a dense one, the most entries a sparse rA held) of the last run"""
         return self._L.cp_solver_reduced_stats(self._h)
+
+    def premultiplied_stats(self):
+        """-> (premultiplied iterations, N > 0, solved from the stored entries
+        of a sparse rA, those that formed a dense rA, the most entries such a
+        sparse rA held) of the last run"""
+        return self._L.cp_solver_premultiplied_stats(self._h)
 
     def stats(self):
         """-> dict: seconds per phase and counts of the last run, and the seconds

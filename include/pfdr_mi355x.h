@@ -538,6 +538,38 @@ int pfdr_cp_reduce_csc_sparse_f64(int N, int V, const pfdr_csc *A, const double 
                                   int normItMax, int normNbInit, int64_t *rnnz,
                                   int64_t *rcolptr, int32_t *rrowidx, double *rval, double *L,
                                   double *Leq);
+/* pfdr_cp_reduce_csc_* at preAt = 1 without the dense rA: rA is the CSC of
+ * pfdr_cp_reduce_csc_sparse_* (not scaled: the premultiplied branch leaves rA
+ * as summed), and rAA = rA^t rA (rV * rV, both triangles) and rY = rA^t Y (rV)
+ * are summed over its stored entries.  rAA[rv + rV ru] adds, for the rows
+ * stored in both columns in ascending order, the products rounded one by one,
+ * from +0, and is +0 where the columns share no row; rY[rv] adds val * Y[row]
+ * over column rv's entries in the same way.  The terms left out are +-0 added
+ * to sums that started at +0, so while the values are finite rAA, rY, Leq
+ * (the roots of rAA's diagonal) and L (the power method of pfdr_cp_reduce_* on
+ * the equilibrated rAA, then the same revert) have the bytes of
+ * pfdr_cp_reduce_csc_* at preAt = 1.  This holds up to rV * rV * N / 2 = 2^34
+ * multiply-adds: above it the dense entry forms rAA on the matrix cores and
+ * the two agree to that Gram's tolerance only; this entry keeps the
+ * reference's order at every size.  Device memory: the entries and rV * rV
+ * reals, never N * rV; no floating atomics, the same bytes on every run.
+ * PFDR_CP_GRAM_WINDOW (rows, >= 1; read at every call) shortens the window of
+ * rows that the Gram kernel holds in LDS, for tests; it changes no byte.
+ * rAA and rY are required, L and Leq may be NULL; rnnz, rcolptr, rrowidx and
+ * rval are all NULL or all set, with the capacities of
+ * pfdr_cp_reduce_csc_sparse_*.  A column of norm 0 is accepted, as the dense
+ * entry accepts it.  The argument and CSC checks are pfdr_cp_reduce_csc_*'s;
+ * arrays host or device per mem. */
+int pfdr_cp_reduce_csc_sparse_preAt_f32(int N, int V, const pfdr_csc *A, const float *Y, int rV,
+                                        const int *rVc, const int *Vc, int mem, float normTol,
+                                        int normItMax, int normNbInit, float *rAA, float *rY,
+                                        float *L, float *Leq, int64_t *rnnz, int64_t *rcolptr,
+                                        int32_t *rrowidx, float *rval);
+int pfdr_cp_reduce_csc_sparse_preAt_f64(int N, int V, const pfdr_csc *A, const double *Y, int rV,
+                                        const int *rVc, const int *Vc, int mem, double normTol,
+                                        int normItMax, int normNbInit, double *rAA, double *rY,
+                                        double *L, double *Leq, int64_t *rnnz, int64_t *rcolptr,
+                                        int32_t *rrowidx, double *rval);
 
 /* ------------------------------------------- cut-pursuit graph steps -- */
 /* The full-graph work of every cut-pursuit iteration around the reduced
@@ -910,15 +942,33 @@ int pfdr_cp_solver_create_sparse(pfdr_cp_solver **out, const pfdr_cp_problem *p,
  * pfdr_cp_solver_set_partition recompute R over the stored entries: the same
  * bytes.  May be called between runs; the state is kept.  PFDR_ERR_ARG naming
  * the offence: a solver not created by pfdr_cp_solver_create_sparse, the
- * simplex kind, an unknown mode. */
+ * simplex kind, an unknown mode.
+ * PFDR_REDUCED_SPARSE_ALL: direct iterations as under PFDR_REDUCED_SPARSE (the
+ * dense fallback for a column of norm 0 included), and the premultiplied
+ * iterations (p->N > 0) keep rA sparse as well: rAA = rA^t rA and rY = rA^t Y
+ * are summed over its stored entries (pfdr_cp_reduce_csc_sparse_preAt_*), PFDR
+ * runs on (rAA, rY) as in the dense mode and the residual walks rA's rows.
+ * The N * rV array is then allocated by the zero-norm fallback only.  A
+ * premultiplied iteration keeps the dense mode's bytes -- L, the iterates and
+ * the residual -- while rV * rV * N / 2 <= 2^34 (above it the dense mode's
+ * Gram leaves the reference's order and this one does not), so a run whose
+ * iterations are all premultiplied equals the dense mode's byte for byte. */
 #define PFDR_REDUCED_DENSE 0
 #define PFDR_REDUCED_SPARSE 1
+#define PFDR_REDUCED_SPARSE_ALL 2
 int pfdr_cp_solver_set_reduced(pfdr_cp_solver *s, int mode);
 /* Of the last run, any may be NULL: the iterations solved on a sparse rA, the
  * direct iterations solved on a dense one (all of them in the dense mode, the
  * zero-norm fallbacks in the sparse mode), the most entries a sparse rA held. */
 int pfdr_cp_solver_reduced_stats(pfdr_cp_solver *s, int64_t *sparse_iterations,
                                  int64_t *dense_direct_iterations, int64_t *max_rnnz);
+/* The same of the last run's premultiplied iterations with p->N > 0 (the
+ * counts above are of the direct ones only), any may be NULL: those solved
+ * from the stored entries of a sparse rA (PFDR_REDUCED_SPARSE_ALL), those that
+ * formed the dense N * rV array (every one in the other two modes), the most
+ * entries such a sparse rA held. */
+int pfdr_cp_solver_premultiplied_stats(pfdr_cp_solver *s, int64_t *sparse_iterations,
+                                       int64_t *dense_iterations, int64_t *max_rnnz);
 void pfdr_cp_solver_destroy(pfdr_cp_solver *s);
 /* Host outputs, any may be NULL: Time[CP_itMax + 1], Obj[CP_itMax + 1],
  * Dif[CP_itMax] of the solver's real type. */

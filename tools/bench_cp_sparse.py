@@ -13,9 +13,11 @@ in one process.  The first run of each is a warm-up (library initialisation,
 allocator cache); --reps further runs of each are reported, every run on a
 fresh solver.  Prints one JSON line.
 
---reduced dense|sparse (one or both) chooses how the sparse solver keeps the
-reduced operator of a direct iteration (pfdr_cp_solver_set_reduced); with both,
-the two modes alternate like the solvers above.  A direct iteration needs
+--reduced dense|sparse|sparse_all (one or several) chooses how the sparse solver
+keeps the reduced operator (pfdr_cp_solver_set_reduced): of a direct iteration
+("sparse"), and of a premultiplied one as well ("sparse_all", whose counts are
+"premultiplied_stats", pfdr_cp_solver_premultiplied_stats); with several, the
+modes alternate like the solvers above.  A direct iteration needs
 rV >= 2 N pit / (N + pit), about twice the previous PFDR iteration count, so
 --pfdr-itmax must be small for a run to take one: the line reports, per mode,
 how many iterations were solved on a sparse rA and how many direct ones on a
@@ -54,8 +56,9 @@ def main():
     ap.add_argument("--CP_itMax", type=int, default=10)
     ap.add_argument("--PFDR_difTol", type=float, default=1e-5)
     ap.add_argument("--PFDR_itMax", "--pfdr-itmax", dest="PFDR_itMax", type=int, default=2000)
-    ap.add_argument("--reduced", nargs="+", choices=["dense", "sparse"], default=["dense"],
-                    help="the sparse solver's reduced operator: one mode, or both alternating")
+    ap.add_argument("--reduced", nargs="+", choices=["dense", "sparse", "sparse_all"],
+                    default=["dense"],
+                    help="the sparse solver's reduced operator: one mode, or several alternating")
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
     from cp_pfdr_graph_d1_amd import pfdr
@@ -98,6 +101,7 @@ def main():
         st = s.stats()
         if A is csc:
             st["reduced"] = s.reduced_stats()
+            st["premultiplied"] = s.premultiplied_stats()
         s.close()
         st["wall"] = time.perf_counter() - t
         st["device_mb"] = device_mb()
@@ -133,6 +137,9 @@ def main():
                                CP_it=last[name][2], rV=int(last[name][1].size),
                                device_mb_after=[s["device_mb"] for s in runs[name]])
                     for name, A, _ in variants if A is csc},
+        "premultiplied_stats": {name: dict(zip(("sparse_iterations", "dense_iterations",
+                                                "max_rnnz"), runs[name][-1]["premultiplied"]))
+                                for name, A, _ in variants if A is csc},
     }
     if args.dense:
         d = last["dense"]
