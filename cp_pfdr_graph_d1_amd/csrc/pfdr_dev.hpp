@@ -109,6 +109,14 @@ __device__ __forceinline__ T block_sum(T v, T *lds /* >= kBlock/64 */) {
 // packed vector of N T (16-byte accesses)
 template <typename T, int N>
 struct alignas(sizeof(T) * N) Pk { T v[N]; };
+template <typename T, int N>
+__device__ __forceinline__ Pk<T, N> ldv(const T *p) {
+    return *reinterpret_cast<const Pk<T, N> *>(p);
+}
+template <typename T, int N>
+__device__ __forceinline__ void stv(T *p, const Pk<T, N> &x) {
+    *reinterpret_cast<Pk<T, N> *>(p) = x;
+}
 
 // s + q[0] + q[1] + ... + q[m-1], left to right, from LDS.  Two register
 // sets A / B of U x 16 bytes: the reads of one set are in flight while the

@@ -35,7 +35,6 @@
 
 #include "pfdr_graph.hpp"
 #include "pfdr_power.hpp"
-#include "pfdr_quadratic_kernels.hpp"
 #include "pfdr_session.hpp"
 
 namespace pfdr {

@@ -47,53 +47,6 @@ __global__ void k_edge_relabel(long E, const unsigned *__restrict__ eorig,
     emap[p] = (int)e;
 }
 
-// tile order: position p takes the edge now at perm[p]; its original id
-// (through eorig when the session was relabelled first) for the incidence
-// keys and the weights' permutation
-__global__ void k_edge_tile_order(long E, const unsigned *__restrict__ perm,
-                                  const unsigned *__restrict__ eorig, const int *__restrict__ Eu,
-                                  const int *__restrict__ Ev, int *__restrict__ nEu,
-                                  int *__restrict__ nEv, unsigned *__restrict__ eo,
-                                  int *__restrict__ emap) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= E) return;
-    const unsigned q = perm[p];
-    nEu[p] = Eu[q];
-    nEv[p] = Ev[q];
-    const unsigned e = eorig ? eorig[q] : q;
-    eo[p] = e;
-    emap[p] = (int)e;
-}
-
-// the same for a partitioned rank: eo = the global edge id (incidence
-// keys), emap = the rank-local position (the caller's per-edge arrays)
-__global__ void k_edge_tile_order_halo(long E, const unsigned *__restrict__ perm,
-                                       const unsigned *__restrict__ eg, long e_offset,
-                                       const int *__restrict__ Eu, const int *__restrict__ Ev,
-                                       int *__restrict__ nEu, int *__restrict__ nEv,
-                                       unsigned *__restrict__ eo, int *__restrict__ emap,
-                                       unsigned *__restrict__ inv) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= E) return;
-    const unsigned q = perm[p];
-    nEu[p] = Eu[q];
-    nEv[p] = Ev[q];
-    eo[p] = eg ? eg[q] : (unsigned)(e_offset + q);
-    emap[p] = (int)q;
-    inv[q] = (unsigned)p;
-}
-
-// the halo's push addresses (side E + e) into the tile order
-__global__ void k_remap_push(long n, long E, const unsigned *__restrict__ inv,
-                             unsigned *__restrict__ addr) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned a = addr[i];
-    const unsigned side = a >= (unsigned)E ? 1u : 0u;
-    addr[i] = side * (unsigned)E + inv[a - side * (unsigned)E];
-}
-
-
 template <typename real>
 class QuadSession final : public IterLoop<real> {
   public:
@@ -222,7 +175,6 @@ class QuadSession final : public IterLoop<real> {
     DevBuf<real> A1_;
     DevBuf<R2<real>> gi_;
     DevBuf<real> rr_;  // per-vertex (cw la0 / Aux) / Ga of the ratio edge sweep (rat())
-    int vpair_cap_ = 0;  // pair vertex sweep: entries of the largest record block (0: off)
     bool rat_on_ = false;  // rr_ formed at setup (see rat())
     real cw_ = real(0);
     DevBuf<real> R_, vpart_, opart_, Obj_, Dif_, csum_;
@@ -238,27 +190,12 @@ class QuadSession final : public IterLoop<real> {
     DevBuf<int> cnt_part_;
     Incidence inc_;
     HostPins pins_;  // caller arrays pinned for the setup copies
-    // split incidence (edges sorted by u): u-run offsets, per-vertex order
-    // masks, addresses of the other entries, per-block path flag
-    DevBuf<int> uptr_, blkok_;
-    DevBuf<unsigned> mask_, oidx_;
-    void build_split();
-    // tiled contributions (tile_sum in pfdr_quadratic_kernels.hpp): large
-    // single-GPU graphs keep their edges sorted by (u block, v block, edge);
-    // d2_ = CSR slot of every contribution address within its vertex block,
-    // ustart_ / tptr_, tstart_, tlen_ = the runs each block stages, tok_ =
-    // blocks whose lists fit the LDS (the others gather through the CSR)
+    // the contribution layouts (pfdr_layout.hpp): large single-GPU graphs and
+    // partitioned ranks keep their edges in tile order (tiled_), the others
+    // get the split incidence where their edges are sorted by u
     bool tiled_ = false;
-    DevBuf<Slots12> slots_;
-    DevBuf<unsigned char> deg8_;  // CSR entries per vertex (tile_sum)
-    DevBuf<unsigned short> luv_;  // both ends mod 256 (k_edge_sweep_tl)
-    DevBuf<int> erec_;            // per edge block: u blocks and v runs (k_edge_sweep_tl)
-    DevBuf<int> ustart_, tptr_, tstart_, tlen_, tok_, trec_;
-    DevBuf<Slots12> ptab_;        // slot patterns of the record blocks' runs (k_run_hash)
-    DevBuf<int> prec_;            // per record block: its runs' offsets into ptab_
-    void build_tiles();
-    void build_patterns(const unsigned short *d2, long n);
-    void build_tile_runs();
+    TileLayout tile_;
+    SplitLayout split_;
     int nbv_, nbe_, nbn_, rows_nb_, rows_cpb_;
 
     void setup_graph(const pfdr_problem *p);
@@ -280,7 +217,6 @@ class QuadSession final : public IterLoop<real> {
     hipStream_t comm_ = nullptr;
     hipEvent_t ev_[4] = {};  // xp ready, pulled, boundary W*Z ready, pushed
     long elo_ = 0, ehi_ = 0;
-    long Eint_ = 0;  // tiled partitioned rank: edges [0, Eint_) have no ghost end
     long zs_ = 0;    // Z layout: 0 half-edge pairs, E side-major (tiled sessions)
     // Z-direct: a tiled single-GPU session with one edge weight and no A1
     // (before any reconditioning) skips the W * Z stores of the edge sweep;
@@ -584,9 +520,7 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool 
     acc(Rpart_.n * sizeof(double));
     acc(sp_.bytes());
     acc((xp_.n + gi_.n) * sizeof(R2<real>) + inc_.ptr.n * 4 + inc_.idx.n * 4);
-    acc((uptr_.n + mask_.n + oidx_.n + blkok_.n) * 4);
-    acc(slots_.n * sizeof(Slots12) + luv_.n * 2 + deg8_.n +
-        (ustart_.n + tptr_.n + tstart_.n + tlen_.n + tok_.n + trec_.n + erec_.n) * 4);
+    acc(split_.bytes() + tile_.bytes());
     if (halo_) {
         plan_overlap();
         // RCCL partitions replay captured chunks too (pull, sweeps, push and
@@ -982,51 +916,14 @@ void QuadSession<real>::setup_graph(const pfdr_problem *p) {
         std::swap(Ev_.p, nv.p);
         eg_ptr = eorig_.p;
     }
-    // tile order of large graphs (see tile_sum): edges sorted by (u block,
-    // v block), stable in the current order; the incidence keys keep the
-    // original edge ids (summation order).  A partitioned rank puts the
-    // edges with a ghost end after the others (the interior ones overlap
-    // the halo pull) and renumbers its push addresses.
+    // tile order of large graphs (pfdr_layout.hpp); the incidence keys keep
+    // the original edge ids (summation order)
     tiled_ = !tiny_ && E_ > 0 && (long)V_ > (long)kFuseBlocks * kBlock;
     if (tiled_) {
-        const int nb = grid_for(Vg_);
-        int vbits = 1;
-        while (vbits < 31 && (1L << vbits) < (long)nb) vbits++;
-        DevBuf<unsigned long long> k(E), ks(E), nint(1);
-        DevBuf<unsigned> v(E), perm(E);
-        k_tile_keys<<<grid_for(E), kBlock, 0, s>>>(E_, Eu_.p, Ev_.p, vbits, k.p, v.p, V_,
-                                                   halo_ != nullptr);
-        PFDR_HIP(hipGetLastError());
-        radix_sort_pairs_stable<unsigned long long>(k.p, ks.p, v.p, perm.p, (long)E,
-                                                    2 * vbits + (halo_ ? 1 : 0), s);
-        if (halo_) k_count_below<<<1, 1, 0, s>>>(E_, ks.p, 1ull << (2 * vbits), nint.p);
-        DevBuf<int> nu(E), nv(E);
-        DevBuf<unsigned> eo(E);
-        emap_.alloc(E);
-        if (halo_) {
-            DevBuf<unsigned> inv(E);
-            k_edge_tile_order_halo<<<grid_for(E), kBlock, 0, s>>>(
-                E_, perm.p, eg.p, e_offset, Eu_.p, Ev_.p, nu.p, nv.p, eo.p, emap_.p, inv.p);
-            const long np = halo_->push_send_off.back();
-            if (np) k_remap_push<<<grid_for(np), kBlock, 0, s>>>(np, E_, inv.p, halo_->push_addr.p);
-            PFDR_HIP(hipGetLastError());
-            unsigned long long ni = 0;
-            PFDR_HIP(hipMemcpyAsync(&ni, nint.p, sizeof(ni), hipMemcpyDeviceToHost, s));
-            PFDR_HIP(hipStreamSynchronize(s));
-            Eint_ = (long)ni;
-            e_offset = 0;
-        } else {
-            k_edge_tile_order<<<grid_for(E), kBlock, 0, s>>>(E_, perm.p, eorig_.p, Eu_.p, Ev_.p,
-                                                             nu.p, nv.p, eo.p, emap_.p);
-            PFDR_HIP(hipGetLastError());
-            PFDR_HIP(hipStreamSynchronize(s));
-            Eint_ = E_;
-        }
-        std::swap(Eu_.p, nu.p);
-        std::swap(Ev_.p, nv.p);
-        std::swap(eorig_.p, eo.p);
-        std::swap(eorig_.n, eo.n);
+        tile_.order(E_, V_, Vg_, Eu_, Ev_, halo_ ? eg.p : eorig_.p, e_offset, eorig_, emap_,
+                    halo_.get(), s);
         eg_ptr = eorig_.p;
+        e_offset = 0;  // (a partitioned rank's keys are global ids now)
     }
     // contributions: local side-major [u ends | v ends] then the received tail
     const long R = halo_ ? halo_->R : 0;
@@ -1034,248 +931,17 @@ void QuadSession<real>::setup_graph(const pfdr_problem *p) {
     contribution_incidence(Eu_.p, Ev_.p, E_, V_, eg_ptr ? eg_ptr : eg.p, e_offset, halo_.get(),
                            inc_, s);
     eorig_.release();
-    if (tiled_) build_tiles();
-    else if (!tiny_) build_split();
-}
-
-// the runs of every vertex block of a tile-ordered graph and the slots of
-// its contributions (see tile_sum)
-template <typename real>
-void QuadSession<real>::build_tiles() {
-    hipStream_t s = stream;
-    const long R = halo_ ? halo_->R : 0;
-    {
-        const long n = 2 * E_ + R, ng = n / kSlotGroup + 1;  // (+1: tile_sum's whole groups)
-        DevBuf<unsigned short> d2(n);
-        k_tile_slots<<<grid_for(V_), kBlock, 0, s>>>(V_, inc_.ptr.p, inc_.idx.p, d2.p);
-        slots_.alloc(ng);
-        k_pack_slots<<<grid_for(ng), kBlock, 0, s>>>(ng, n, d2.p, slots_.p);
-        PFDR_HIP(hipGetLastError());
-        build_tile_runs();
-        build_patterns(d2.p, n);
-    }  // (d2's block is reused only once the stream is idle, dev_free)
-}
-
-// the record and run tables of the tiled blocks (see tile_sum)
-template <typename real>
-void QuadSession<real>::build_tile_runs() {
-    hipStream_t s = stream;
-    const int nb = grid_for(V_);
-    const long R = halo_ ? halo_->R : 0;
-    luv_.alloc((size_t)E_);
-    k_tile_luv<<<grid_for(E_), kBlock, 0, s>>>(E_, Eu_.p, Ev_.p, luv_.p);
-    {
-        constexpr int EB = kBlock * Vec<real>::kPer16B;  // edges per k_edge_sweep_tl block
-        const int neb = (int)((E_ + EB - 1) / EB);
-        erec_.alloc((size_t)neb * kErec);
-        k_tile_erec<<<(neb + kBlock / kWave - 1) / (kBlock / kWave), kBlock, 0, s>>>(
-            E_, EB, 0, neb, Eu_.p, Ev_.p, erec_.p);
-        PFDR_HIP(hipGetLastError());
+    if (tiled_) {
+        tile_.build(E_, V_, Eu_.p, Ev_.p, inc_, halo_.get(), sizeof(real), s);
+        tiled_blocks = tile_.tiled_blocks;
+        record_blocks = tile_.record_blocks;
+        slot_patterns = tile_.slot_patterns;
+        vertex_pair = tile_.vpair_cap;
+    } else if (!tiny_) {
+        split_.build(E_, V_, Eu_.p, inc_, GatherCap<real>::v / 2, s);
+        split_blocks = split_.split_blocks;
+        if (split_.uptr.p) ustaged = us_ ? 1 : 0;
     }
-    ustart_.alloc((size_t)nb + 1);
-    // u runs: the interior edges (sorted by u block); a partitioned rank's
-    // boundary edges [Eint_, E) add their owned u ends as runs, its received
-    // contributions theirs (k_tile_runs_count)
-    k_tile_ustart<<<grid_for(Eint_ + 1), kBlock, 0, s>>>(Eint_, nb, Eu_.p, ustart_.p);
-    DevBuf<int> cnt(nb), fill(nb);
-    PFDR_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * nb, s));
-    PFDR_HIP(hipMemsetAsync(fill.p, 0, sizeof(int) * nb, s));
-    struct Src { long n; const int *a; const unsigned long long *keys; long rs; };
-    const Src src[3] = {{E_, Ev_.p, nullptr, 0},
-                        {E_ - Eint_, Eu_.p + Eint_, nullptr, Eint_ - E_},
-                        {R, nullptr, halo_ ? halo_->recv_keys.p : nullptr, E_}};
-    for (const Src &q : src)
-        if (q.n > 0) k_tile_runs_count<<<grid_for(q.n), kBlock, 0, s>>>(q.n, q.a, q.keys, V_, cnt.p);
-    PFDR_HIP(hipGetLastError());
-    std::vector<int> h(nb), tp((size_t)nb + 1, 0);
-    PFDR_HIP(hipMemcpyAsync(h.data(), cnt.p, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    for (int b = 0; b < nb; b++) tp[b + 1] = tp[b] + h[b];
-    const int nruns = tp[nb];
-    tptr_.alloc((size_t)nb + 1);
-    PFDR_HIP(hipMemcpyAsync(tptr_.p, tp.data(), sizeof(int) * (nb + 1), hipMemcpyHostToDevice, s));
-    tstart_.alloc(nruns ? nruns : 1);
-    tlen_.alloc(nruns ? nruns : 1);
-    for (const Src &q : src)
-        if (q.n > 0)
-            k_tile_runs_fill<<<grid_for(q.n), kBlock, 0, s>>>(q.n, q.a, q.keys, V_, q.rs, tptr_.p,
-                                                              fill.p, tstart_.p, tlen_.p);
-    tok_.alloc(nb);
-    k_tile_ok<<<grid_for(nb), kBlock, 0, s>>>(V_, nb, inc_.ptr.p, tptr_.p, kTileCap, tok_.p);
-    trec_.alloc((size_t)nb * kTileRec);
-    k_tile_rec<<<grid_for(nb), kBlock, 0, s>>>(nb, ustart_.p, tptr_.p, tstart_.p, tlen_.p, tok_.p,
-                                               trec_.p);
-    deg8_.alloc(V_);
-    k_tile_deg<<<grid_for(V_), kBlock, 0, s>>>(V_, inc_.ptr.p, deg8_.p);
-    PFDR_HIP(hipGetLastError());
-    PFDR_HIP(hipMemcpyAsync(h.data(), tok_.p, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    long n = 0, nr = 0;
-    for (int x : h) {
-        n += x != 0;
-        nr += x == 2;
-    }
-    tiled_blocks = n;
-    record_blocks = nr;
-    // the pair vertex sweep (k_vertex_sweep_pair): f32 sessions whose every
-    // block is a record block, when two blocks' lists still leave LDS for
-    // seven workgroups per CU (the kernel's seven waves per SIMD): C5 (6
-    // entries per vertex) vertex sweep 3.15-3.22 -> 2.83-2.85 ms, C2 -2 %;
-    // the headline's 12 per vertex would halve the resident workgroups
-    // (0.174 -> 0.226 ms, f6j), so it keeps the one-block sweep.
-    // PFDR_VPAIR=0: the one-block sweep throughout
-    const char *e = getenv("PFDR_VPAIR");
-    if (sizeof(real) == 4 && nr == nb && !(e && e[0] == '0')) {
-        DevBuf<int> ent(nb);
-        k_rec_entries<<<grid_for(nb), kBlock, 0, s>>>(V_, nb, inc_.ptr.p, tok_.p, ent.p);
-        PFDR_HIP(hipGetLastError());
-        PFDR_HIP(hipMemcpyAsync(h.data(), ent.p, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-        const int cap = std::max(1, *std::max_element(h.begin(), h.end()));
-        const size_t per_wg = 2 * (size_t)cap * sizeof(real) + 2048;  // (+ the static arrays)
-        if (per_wg * 7 <= 160 * 1024) vpair_cap_ = cap;
-        vertex_pair = vpair_cap_;
-    }
-}
-
-// Slot patterns (k_run_hash): when the record blocks' runs repeat a few
-// slot sequences (regular grids), the distinct ones go to a small table
-// (ptab_) and each block's runs point into it (prec_), so the vertex sweep
-// streams no per-entry slots; runs that hash alike are verified equal
-// entry by entry (k_run_verify) before the table is used.  Off when the
-// patterns do not repeat (the jittered headline) or PFDR_TILE_PATTERNS=0.
-template <typename real>
-void QuadSession<real>::build_patterns(const unsigned short *d2, long n) {
-    const char *e = getenv("PFDR_TILE_PATTERNS");
-    if ((e && e[0] == '0') || !record_blocks) return;
-    hipStream_t s = stream;
-    const int nb = grid_for(V_);
-    const long nr = (long)nb * kPrec;
-    std::vector<unsigned long long> hh(nr);
-    std::vector<int> rec((size_t)nb * kTileRec);
-    {
-        DevBuf<unsigned long long> h(nr);
-        k_run_hash<<<grid_for(nr), kBlock, 0, s>>>(nb, E_, tok_.p, trec_.p, d2, h.p);
-        PFDR_HIP(hipGetLastError());
-        PFDR_HIP(hipMemcpyAsync(hh.data(), h.p, sizeof(unsigned long long) * nr,
-                                hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipMemcpyAsync(rec.data(), trec_.p, sizeof(int) * rec.size(),
-                                hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-    }
-    constexpr size_t kMaxPatterns = 65536;
-    std::unordered_map<unsigned long long, int> pat;
-    std::vector<long long> pA;
-    std::vector<int> pLen, pOff, prec(nr, 0);
-    std::vector<long long> repA(nr, -1);
-    long groups = 0;
-    for (long id = 0; id < nr; id++) {
-        if (hh[id] == ~0ull) continue;
-        auto it = pat.find(hh[id]);
-        int pi;
-        if (it == pat.end()) {
-            const int b = (int)(id / kPrec), q = (int)(id % kPrec);
-            const int *r = &rec[(size_t)b * kTileRec];
-            const long long A = q == 0 ? r[0] : E_ + r[1 + 2 * q];
-            const int len = q == 0 ? r[1] : r[2 + 2 * q];
-            pi = (int)pA.size();
-            pat.emplace(hh[id], pi);
-            pA.push_back(A);
-            pLen.push_back(len);
-            pOff.push_back((int)groups);
-            groups += ((A & 7) + len + 7) / 8;
-            if (pat.size() > kMaxPatterns || groups * kSlotGroup > n / 4) return;  // no repeats
-        } else {
-            pi = it->second;
-        }
-        prec[id] = pOff[pi];
-        repA[id] = pA[pi];
-    }
-    if (!groups) return;
-    {   // same hash, same slots: checked entry by entry on the device
-        DevBuf<long long> dr(nr);
-        DevBuf<int> bad(1);
-        PFDR_HIP(hipMemcpyAsync(dr.p, repA.data(), sizeof(long long) * nr, hipMemcpyHostToDevice, s));
-        PFDR_HIP(hipMemsetAsync(bad.p, 0, sizeof(int), s));
-        k_run_verify<<<grid_for(nr), kBlock, 0, s>>>(nb, E_, tok_.p, trec_.p, d2, dr.p, bad.p);
-        PFDR_HIP(hipGetLastError());
-        int hb = 1;
-        PFDR_HIP(hipMemcpyAsync(&hb, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-        if (hb) return;
-    }
-    // the table: each pattern's groups packed from its representative's
-    // slots (12 bits each, as k_pack_slots; entries outside the run are 0)
-    std::vector<Slots12> tab((size_t)groups);
-    std::vector<unsigned short> sl;
-    for (size_t pi = 0; pi < pA.size(); pi++) {
-        const long long A = pA[pi], g0 = A / kSlotGroup;
-        const int len = pLen[pi];
-        const long gn = ((A & 7) + len + 7) / 8;
-        if (!gn) continue;
-        sl.assign((size_t)gn * kSlotGroup, 0);
-        PFDR_HIP(hipMemcpy(sl.data() + (A - g0 * kSlotGroup), d2 + A, sizeof(unsigned short) * len,
-                           hipMemcpyDeviceToHost));
-        for (long g = 0; g < gn; g++) {
-            unsigned long long lo = 0, hi = 0;
-            for (int q = 0; q < kSlotGroup; q++) {
-                const unsigned long long x = sl[(size_t)g * kSlotGroup + q] & 0xfffu;
-                const int bit = 12 * q;
-                if (bit + 12 <= 64) lo |= x << bit;
-                else if (bit >= 64) hi |= x << (bit - 64);
-                else { lo |= x << bit; hi |= x >> (64 - bit); }
-            }
-            Slots12 &t = tab[(size_t)pOff[pi] + g];
-            t.w[0] = (unsigned)lo;
-            t.w[1] = (unsigned)(lo >> 32);
-            t.w[2] = (unsigned)hi;
-        }
-    }
-    ptab_.alloc((size_t)groups);
-    prec_.alloc((size_t)nr);
-    PFDR_HIP(hipMemcpyAsync(ptab_.p, tab.data(), sizeof(Slots12) * groups, hipMemcpyHostToDevice, s));
-    PFDR_HIP(hipMemcpyAsync(prec_.p, prec.data(), sizeof(int) * nr, hipMemcpyHostToDevice, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    slot_patterns = (int64_t)pA.size();
-}
-
-// Split incidence for the vertex sweep (split_sum): when the edges are
-// sorted by their u end (natural emission order, relabelled sessions), each
-// vertex's u-end contributions are a contiguous run of wz and need no
-// address.  Blocks that do not qualify keep the CSR gather.
-template <typename real>
-void QuadSession<real>::build_split() {
-    if (!E_) return;
-    hipStream_t s = stream;
-    DevBuf<unsigned long long> bad(1);
-    PFDR_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
-    k_u_order_check<<<grid_for(E_), kBlock, 0, s>>>(E_, V_, Eu_.p, bad.p);
-    PFDR_HIP(hipGetLastError());
-    unsigned long long nbad = 0;
-    PFDR_HIP(hipMemcpyAsync(&nbad, bad.p, sizeof(nbad), hipMemcpyDeviceToHost, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    if (nbad) return;
-    const int nb = grid_for(V_);
-    const long ototal = inc_.n - E_;  // every local edge's u end is an owned row
-    if (ototal < 0) return;
-    uptr_.alloc((size_t)V_ + 1);
-    k_uptr<<<grid_for(E_ + 1), kBlock, 0, s>>>(E_, V_, Eu_.p, uptr_.p);
-    PFDR_HIP(hipGetLastError());
-    ustaged = us_ ? 1 : 0;
-    mask_.alloc(V_);
-    oidx_.alloc(ototal ? ototal : 1);
-    blkok_.alloc(nb);
-    k_split_build<<<nb, kBlock, 0, s>>>(V_, E_, inc_.ptr.p, inc_.idx.p, uptr_.p, ototal, mask_.p,
-                                        oidx_.p, blkok_.p, GatherCap<real>::v / 2);
-    PFDR_HIP(hipGetLastError());
-    std::vector<int> h(nb);
-    PFDR_HIP(hipMemcpyAsync(h.data(), blkok_.p, nb * sizeof(int), hipMemcpyDeviceToHost, s));
-    PFDR_HIP(hipStreamSynchronize(s));
-    long n = 0;
-    for (int x : h) n += x;
-    split_blocks = n;
-    if (!n) { mask_.release(); oidx_.release(); blkok_.release(); }  // uptr_ serves the edge sweep
-    ustaged = us_ ? 1 : 0;
 }
 
 // R = Y - A X (direct mode), gated
@@ -1607,15 +1273,15 @@ void QuadSession<real>::edge_sweep(long ebeg, long eend, const Ctrl<real> *c, co
         auto k = rr_.p ? k_edge_sweep_tl<real, true, true>
                  : (!la_it() && !A1_.p) ? k_edge_sweep_tl<real, true>
                                         : k_edge_sweep_tl<real, false>;
-        k<<<g, kBlock, 0, s>>>(E_, V_, Eu_.p, luv_.p, erec_.p, Ev_.p, xr_, Z2_.p, A1_.p, cw_,
-                               gi_.p, la_it(), la0_, zdirect() ? nullptr : wz_.p, rho_, c,
+        k<<<g, kBlock, 0, s>>>(E_, V_, Eu_.p, tile_.luv.p, tile_.erec.p, Ev_.p, xr_, Z2_.p, A1_.p,
+                               cw_, gi_.p, la_it(), la0_, zdirect() ? nullptr : wz_.p, rho_, c,
                                (int)(ebeg / EB), nb, xm, rr_.p);
         return;
     }
     if (tiled_) throw std::logic_error("tiled edge sweep: range not on edge blocks");
-    if (us_ && uptr_.p) {
+    if (us_ && split_.uptr.p) {
         auto k = fuse_ ? k_edge_sweep_us<real, true> : k_edge_sweep_us<real, false>;
-        k<<<g, kBlock, 0, s>>>(E_, Eu_.p, Ev_.p, uptr_.p, xr_, Z2_.p, A1_.p, cw_, gi_.p,
+        k<<<g, kBlock, 0, s>>>(E_, Eu_.p, Ev_.p, split_.uptr.p, xr_, Z2_.p, A1_.p, cw_, gi_.p,
                                la_it(), la0_, wz_.p, rho_, c, nb, xm, rg, f, pad_out());
     } else {
         auto k = fuse_ ? k_edge_sweep<real, true> : k_edge_sweep<real, false>;
@@ -1643,7 +1309,8 @@ VArgs<real> QuadSession<real>::vargs(int bbeg, int bend, const Ctrl<real> *c) {
     VArgs<real> a{};
     a.V = V_; a.ptr = inc_.ptr.p; a.idx = inc_.idx.p; a.xp = xr_; a.wz = wz_.p;
     a.xpo = xw_ == xr_ ? nullptr : xw_;
-    a.uptr = uptr_.p; a.mask = mask_.p; a.oidx = oidx_.p; a.blkok = blkok_.p;
+    a.uptr = split_.uptr.p; a.mask = split_.mask.p; a.oidx = split_.oidx.p;
+    a.blkok = split_.blkok.p;
     a.Y = Y_.p; a.A = A_.p; a.Ga = Ga_.p; a.Th_l1 = Th_l1_.p;
     a.prox = prox_; a.positivity = positivity_; a.lo = lo_; a.hi = hi_;
     a.fwd = mode_ == A_IDENT ? 1 : (mode_ == A_DIAG ? 2 : 0);
@@ -1651,8 +1318,10 @@ VArgs<real> QuadSession<real>::vargs(int bbeg, int bend, const Ctrl<real> *c) {
     a.late = fuse_ ? 1 : 0;
     a.E = E_;
     if (tiled_) {
-        a.slots = slots_.p; a.trec = trec_.p; a.ptab = ptab_.p; a.prec = prec_.p; a.deg8 = deg8_.p; a.ustart = ustart_.p; a.tptr = tptr_.p; a.tstart = tstart_.p;
-        a.tlen = tlen_.p; a.tok = tok_.p;
+        const TileLayout &t = tile_;
+        a.slots = t.slots.p; a.trec = t.trec.p; a.ptab = t.ptab.p; a.prec = t.prec.p;
+        a.deg8 = t.deg8.p; a.ustart = t.ustart.p; a.tptr = t.tptr.p; a.tstart = t.tstart.p;
+        a.tlen = t.tlen.p; a.tok = t.tok.p;
         a.zs = Z2_.p; a.invAux = invAux_.p; a.a0 = cw_ * la0_;
         a.gi = gi_.p;  // (Ga, 1/Aux) in one load
     }
@@ -1685,9 +1354,9 @@ void QuadSession<real>::vertex_sweep(int bbeg, int bend, const Ctrl<real> *c, co
             a, wzp_.p, pad_nmax_, ends_ ? pidx_.p : nullptr, ends_ ? xpe_.p : nullptr);
         return;
     }
-    if (vpair_cap_ && bend2 <= bbeg2 && a.nb >= 2) {  // pairs of record blocks, one range
+    if (tile_.vpair_cap && bend2 <= bbeg2 && a.nb >= 2) {  // pairs of record blocks, one range
         const int np = a.nb / 2;
-        const size_t lb = 2 * (size_t)vpair_cap_ * sizeof(real);
+        const size_t lb = 2 * (size_t)tile_.vpair_cap * sizeof(real);
         if (a.nb & 1) {  // the odd last block first, on its own
             VArgs<real> a1 = a;
             a1.bbeg = a.bbeg + a.nb - 1;
@@ -1699,8 +1368,8 @@ void QuadSession<real>::vertex_sweep(int bbeg, int bend, const Ctrl<real> *c, co
         }
         a.xcd = xcd_fit(np, xcd_v_);
         const int g = xcd_grid(np, a.xcd);
-        if (zdirect()) k_vertex_sweep_pair<real, true><<<g, kBlock, lb, s>>>(a, vpair_cap_);
-        else k_vertex_sweep_pair<real><<<g, kBlock, lb, s>>>(a, vpair_cap_);
+        if (zdirect()) k_vertex_sweep_pair<real, true><<<g, kBlock, lb, s>>>(a, tile_.vpair_cap);
+        else k_vertex_sweep_pair<real><<<g, kBlock, lb, s>>>(a, tile_.vpair_cap);
         return;
     }
     if (zdirect())
@@ -1853,7 +1522,7 @@ void QuadSession<real>::plan_overlap() {
     if (tiled_) {  // tile order: the interior edges come first, cut on whole edge blocks
         constexpr long EB = kBlock * EPT;
         elo_ = 0;
-        ehi_ = (Eint_ / EB) * EB;
+        ehi_ = (tile_.Eint / EB) * EB;
     }
     // vertex blocks: any CSR entry from the received tail
     std::vector<int> ptr(V_ + 1);
@@ -2058,49 +1727,4 @@ extern "C" int pfdr_quadratic_d1_bounds_csc_f64(int V, int E, int N, double *X, 
     return quadratic_host<double>("pfdr_quadratic_d1_bounds_csc_f64", PFDR_KIND_BOUNDS, V, E, N,
                                   X, Y, nullptr, Eu, Ev, La_d1, nullptr, 0, min, max, Ltype, L,
                                   rho, condMin, difRcd, difTol, itMax, it, Obj, Dif, verbose, &A);
-}
-
-// Test hook (pfdr_mi355x.h, "debug"): the edge-block records of
-// k_edge_sweep_tl for host arrays; only blocks [blk_begin, blk_begin +
-// blk_count) are built, every other record keeps the caller's contents.
-extern "C" int pfdr_debug_tile_erec(int64_t E, int dtype, const int *Eu, const int *Ev,
-                                    int blk_begin, int blk_count, int *rec, int64_t rec_ints) {
-    using namespace pfdr;
-    const char *fn = "pfdr_debug_tile_erec";
-    try {
-        if (E <= 0 || !Eu || !Ev || !rec || (dtype != PFDR_F32 && dtype != PFDR_F64))
-            return report_error(fn, "invalid argument");
-        const int EB = kBlock * (dtype == PFDR_F32 ? Vec<float>::kPer16B : Vec<double>::kPer16B);
-        const long neb = (E + EB - 1) / EB;
-        if (rec_ints != neb * kErec || blk_begin < 0 || blk_count < 0 || blk_begin + blk_count > neb)
-            return report_error(fn, "record array or block range does not match E");
-        hipStream_t s = lib_stream();
-        DevBuf<int> dEu(E), dEv(E), dr(rec_ints);
-        PFDR_HIP(hipMemcpyAsync(dEu.p, Eu, E * 4, hipMemcpyHostToDevice, s));
-        PFDR_HIP(hipMemcpyAsync(dEv.p, Ev, E * 4, hipMemcpyHostToDevice, s));
-        PFDR_HIP(hipMemcpyAsync(dr.p, rec, rec_ints * 4, hipMemcpyHostToDevice, s));
-        if (blk_count) {
-            const int wpb = kBlock / kWave;
-            k_tile_erec<<<(blk_count + wpb - 1) / wpb, kBlock, 0, s>>>(E, EB, blk_begin,
-                                                                     blk_begin + blk_count, dEu.p,
-                                                                     dEv.p, dr.p);
-            PFDR_HIP(hipGetLastError());
-        }
-        PFDR_HIP(hipMemcpyAsync(rec, dr.p, rec_ints * 4, hipMemcpyDeviceToHost, s));
-        PFDR_HIP(hipStreamSynchronize(s));
-    } catch (const HipError &h) {
-        return report_error(fn, h);
-    } catch (const std::exception &ex) {
-        return report_error(fn, ex.what());
-    }
-    return PFDR_OK;
-}
-
-// the record layout the hook writes: ints per record, v runs per record,
-// nub of an unstaged (u-block drop) block
-extern "C" int pfdr_debug_erec_layout(int *ints, int *runs, int *nostage) {
-    if (ints) *ints = pfdr::kErec;
-    if (runs) *runs = pfdr::kEbRuns;
-    if (nostage) *nostage = pfdr::kErecNoStage;
-    return PFDR_OK;
 }

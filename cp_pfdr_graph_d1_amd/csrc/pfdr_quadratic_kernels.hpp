@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "pfdr_graph.hpp"
+#include "pfdr_layout.hpp"
 #include "pfdr_monosum.hpp"
 #include "pfdr_session.hpp"
 
@@ -49,15 +50,6 @@ enum Gate : int { GATE_NONE = 0, GATE_ACTIVE = 1, GATE_OBJ = 2,
                   GATE_ACTIVE_OR_OBJ = 3 };
 
 template <typename real> using R2 = typename Vec<real>::v2;
-
-template <typename T, int N>
-__device__ __forceinline__ Pk<T, N> ldv(const T *p) {
-    return *reinterpret_cast<const Pk<T, N> *>(p);
-}
-template <typename T, int N>
-__device__ __forceinline__ void stv(T *p, const Pk<T, N> &x) {
-    *reinterpret_cast<Pk<T, N> *>(p) = x;
-}
 
 template <typename real>
 __device__ __forceinline__ bool gated(const Ctrl<real> *c, int gate) {
@@ -209,39 +201,7 @@ __device__ __forceinline__ real split_sum(int V, int v0, int v, const int *__res
 }
 
 // ---------------------------------------------- tiled DR contributions --
-// Large single-GPU graphs store their edges in TILE order: sorted by
-// (u block, v block, edge), 256-vertex blocks (the vertex sweep's).  The
-// edge sweep then writes both contributions W*Z at the edge's position
-// (wz[p] u end, wz[E + p] v end) as plain streams, and every vertex block
-// finds ALL of its contributions in a few contiguous runs: the u ends of
-// its own block's edges (wz[ustart[b] .. ustart[b+1]), one run) and the
-// v ends of the (u block, b) tiles (runs of wz[E + p] listed in tptr /
-// tstart / tlen).  Each run is read once, coalesced, by exactly one
-// workgroup; every entry carries its slot in the block's CSR-ordered list
-// (d2, 16 bits, the CSR position of (edge, side) minus the block's first),
-// so staging puts each contribution where the reference's (e, side) order
-// wants it, and each lane then adds its vertex's slots in order -- the sums
-// of gather_sum / split_sum bit for bit, without a single gathered load.
-constexpr int kTileCap = 4096;  // staged entries per vertex block (LDS: GatherCap)
-
-// Each vertex's slots [my0, my0 + deg) in the block's list come from its
-// degree (deg8: one byte per vertex, < 256 in every tiled block -- k_tile_ok)
-// by a block scan, instead of two CSR pointers (1 B per vertex, not 4).
-// The slots are 12-bit (a tiled block lists at most kTileCap = 4096
-// contributions), packed eight to a 12-byte group (Slots12), and the runs
-// are staged a group at a time: one 12-byte slot load beside the group's
-// contributions (two 16-byte loads f32, four f64), from the aligned group
-// at or below each run's start, elements outside the run dropped.  The
-// contribution arrays carry one spare group at their end for the last
-// run's tail.
-constexpr int kTileRuns = 128;  // v-end runs per vertex block
-constexpr int kSlotGroup = 8;   // contributions per packed slot group
-struct alignas(4) Slots12 { unsigned w[3]; };  // 8 x 12 bits, little-endian
-__device__ __forceinline__ int slot12(const Slots12 &g, int i) {
-    const unsigned long long lo = g.w[0] | ((unsigned long long)g.w[1] << 32);  // bits 0..63
-    const unsigned long long hi = g.w[1] | ((unsigned long long)g.w[2] << 32);  // bits 32..95
-    return i < 5 ? (int)((lo >> (12 * i)) & 0xfff) : (int)((hi >> (12 * i - 32)) & 0xfff);
-}
+// the ordered sum of a tiled vertex block from its runs (formats: pfdr_layout.hpp)
 
 template <typename real, int GB, bool ZD = false>
 __device__ __forceinline__ real tile_sum(int V, long E, int blk, int v,
@@ -373,14 +333,10 @@ __device__ __forceinline__ real tile_sum(int V, long E, int blk, int v,
     return s;
 }
 
-// tile_sum from a per-block record (blocks with at most kRecRuns v-end runs,
-// tok = 2): [u start, u count, runs, (start, length) x runs] in 32 ints, so
-// the block's metadata is ONE load round (the run table otherwise costs two
-// dependent ones, tptr then tstart / tlen, and a barrier), every wave holds
-// the runs in its lanes, and the u-end and v-end groups are loaded in the
-// same round -- two groups in flight per lane -- before one barrier.
-constexpr int kRecRuns = 14, kTileRec = 32;
-constexpr int kPrec = 16;  // runs per block in prec: the u run, then up to 15 v runs
+// tile_sum for a record block (tok = 2, pfdr_layout.hpp): every wave holds
+// the runs of the block's record in its lanes, and the u-end and v-end
+// groups are loaded in the same round -- two groups in flight per lane --
+// before one barrier.
 
 template <typename real, bool ZD = false>
 __device__ __forceinline__ real tile_sum_rec(int V, long E, int blk, int v,
@@ -620,288 +576,6 @@ __device__ __forceinline__ void tile_sum_rec2(int V, long E, int b0, int v0, int
     for (int j = 0; j < dg1; j++) s1 += ZD ? wv1 * lds[cap + my1 + j] : lds[cap + my1 + j];
     x0 = s0;
     x1 = s1;
-}
-
-// tile-order keys: (u block, v block) in the high bits, edge position the
-// value; a partitioned rank (split) puts the edges with a ghost end after
-// all the others (bit 2 vbits)
-static __global__ void k_tile_keys(long E, const int *__restrict__ Eu, const int *__restrict__ Ev,
-                                   int vbits, unsigned long long *__restrict__ keys,
-                                   unsigned *__restrict__ vals, int V = 0, bool split = false) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const int u = Eu[e], v = Ev[e];
-    const unsigned long long g = split && (u >= V || v >= V) ? 1ull << (2 * vbits) : 0ull;
-    keys[e] = g | ((unsigned long long)(u / kBlock) << vbits) | (unsigned)(v / kBlock);
-    vals[e] = (unsigned)e;
-}
-
-// *out = the number of sorted keys below `bound` (one lane, binary search)
-static __global__ void k_count_below(long n, const unsigned long long *__restrict__ keys,
-                                     unsigned long long bound, unsigned long long *out) {
-    long lo = 0, hi = n;
-    while (lo < hi) {
-        const long mid = (lo + hi) >> 1;
-        if (keys[mid] < bound) lo = mid + 1;
-        else hi = mid;
-    }
-    *out = (unsigned long long)lo;
-}
-
-// d2[address] = CSR slot of the (edge, side) at that address, relative to the
-// first slot of its vertex block; one lane per vertex
-static __global__ void k_tile_slots(int V, const int *__restrict__ ptr,
-                                    const unsigned *__restrict__ idx,
-                                    unsigned short *__restrict__ d2) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= V) return;
-    const int base = ptr[v - v % kBlock];
-    for (int j = ptr[v]; j < ptr[v + 1]; j++) d2[idx[j]] = (unsigned short)(j - base);
-}
-
-// the slots of addresses [8 g, 8 g + 8) packed into group g (12 bits each,
-// slot i at bits [12 i, 12 i + 12); a tiled block's slots are < kTileCap)
-static __global__ void k_pack_slots(long ngroups, long n, const unsigned short *__restrict__ d2,
-                                    Slots12 *__restrict__ out) {
-    const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ngroups) return;
-    unsigned long long lo = 0, hi = 0;  // bits 0..63, 64..95
-#pragma unroll
-    for (int q = 0; q < kSlotGroup; q++) {
-        const long p = g * kSlotGroup + q;
-        const unsigned long long x = p < n ? (d2[p] & 0xfffu) : 0u;
-        const int bit = 12 * q;
-        if (bit + 12 <= 64) {
-            lo |= x << bit;
-        } else if (bit >= 64) {
-            hi |= x << (bit - 64);
-        } else {
-            lo |= x << bit;
-            hi |= x >> (64 - bit);
-        }
-    }
-    Slots12 r;
-    r.w[0] = (unsigned)lo;
-    r.w[1] = (unsigned)(lo >> 32);
-    r.w[2] = (unsigned)hi;
-    out[g] = r;
-}
-
-// ustart[b] = first position whose u end is in block >= b (tile order sorts by
-// u block), ustart[nb] = E
-static __global__ void k_tile_ustart(long E, int nb, const int *__restrict__ Eu,
-                                     int *__restrict__ ustart) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > E) return;
-    const int lo = p == 0 ? 0 : Eu[p - 1] / kBlock + 1;
-    const int hi = p == E ? nb : Eu[p] / kBlock;
-    for (int b = lo; b <= hi; b++) ustart[b] = (int)p;
-}
-
-// Runs of a vertex block's contributions outside its u run, each a maximal
-// stretch of entries i of one source whose vertex lies in that block:
-//   v ends (a = Ev over [0, E), rs = 0): wz[E + i];
-//   u ends of a partitioned rank's boundary edges (a = Eu + Eint, rs = Eint - E):
-//     wz[Eint + i];
-//   received contributions (keys = the halo's recv_keys, rs = E): wz[2E + i];
-// vertices >= V (ghosts) belong to no block.  A run is stored as its start
-// relative to E (tstart = rs + i: the vertex sweep reads wz[E + tstart + k])
-// and its length.
-__device__ __forceinline__ int run_block(long i, const int *__restrict__ a,
-                                         const unsigned long long *__restrict__ keys, int V) {
-    const int x = keys ? (int)(keys[i] >> 32) : a[i];
-    return x < V ? x / kBlock : -1;
-}
-static __global__ void k_tile_runs_count(long n, const int *__restrict__ a,
-                                         const unsigned long long *__restrict__ keys, int V,
-                                         int *__restrict__ cnt) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int b = run_block(i, a, keys, V);
-    if (b >= 0 && (i == 0 || run_block(i - 1, a, keys, V) != b)) atomicAdd(cnt + b, 1);
-}
-
-// each run at its block's next slot (the order of a block's runs does not
-// matter: every entry carries its slot), with its length
-static __global__ void k_tile_runs_fill(long n, const int *__restrict__ a,
-                                        const unsigned long long *__restrict__ keys, int V,
-                                        long rs, const int *__restrict__ tptr,
-                                        int *__restrict__ fill, int *__restrict__ tstart,
-                                        int *__restrict__ tlen) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int b = run_block(i, a, keys, V);
-    if (b < 0 || (i != 0 && run_block(i - 1, a, keys, V) == b)) return;
-    long q = i + 1;
-    while (q < n && run_block(q, a, keys, V) == b) q++;
-    const int j = tptr[b] + atomicAdd(fill + b, 1);
-    tstart[j] = (int)(rs + i);
-    tlen[j] = (int)(q - i);
-}
-
-// tok[b] = 1 when block b's entries fit the LDS list and its runs the table
-// tok[b] = 1: block b's list fits the LDS (cap entries), its runs the run
-// table, and every degree a byte (deg8, tile_sum)
-static __global__ void k_tile_ok(int V, int nb, const int *__restrict__ ptr,
-                                 const int *__restrict__ tptr, int cap, int *__restrict__ tok) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    const int v0 = b * kBlock, v1 = min(v0 + kBlock, V);
-    bool ok = ptr[v1] - ptr[v0] <= cap && tptr[b + 1] - tptr[b] <= kTileRuns;
-    for (int v = v0; ok && v < v1; v++) ok = ptr[v + 1] - ptr[v] < 256;
-    tok[b] = ok ? 1 : 0;
-}
-
-// the per-block records of tile_sum_rec for tiled blocks with at most
-// kRecRuns v-end runs (tok 1 -> 2)
-static __global__ void k_tile_rec(int nb, const int *__restrict__ ustart,
-                                  const int *__restrict__ tptr, const int *__restrict__ tstart,
-                                  const int *__restrict__ tlen, int *__restrict__ tok,
-                                  int *__restrict__ rec) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    const int t0 = tptr[b], nt = tptr[b + 1] - t0;
-    int *r = rec + (long)b * kTileRec;
-    for (int q = 0; q < kTileRec; q++) r[q] = 0;
-    if (!tok[b] || nt > kRecRuns) return;
-    r[0] = ustart[b];
-    r[1] = ustart[b + 1] - ustart[b];
-    r[2] = nt;
-    for (int q = 0; q < nt; q++) {
-        r[3 + 2 * q] = tstart[t0 + q];
-        r[4 + 2 * q] = tlen[t0 + q];
-    }
-    tok[b] = 2;
-}
-
-// ------------------------------------------------ slot patterns -------
-// On regular graphs most record blocks' runs carry the same slot sequences
-// (on C2 every interior block is one x-row of the grid; on C5 the 640-vertex
-// rows give five phases).  A run's PATTERN = (its first address mod 8, its
-// length, its slots); the distinct patterns go to a small table of packed
-// groups (ptab, aligned as each run's groups are) and each record block gets
-// the table offset of every run (prec: 16 ints beside its record), so the
-// vertex sweep reads no per-entry slot stream (12 B per 8 contributions).
-__device__ __forceinline__ bool rec_run(const int *r, long E, int q, long &A, int &len) {
-    const int nt = r[2];
-    if (q == 0) {
-        A = r[0];
-        len = r[1];
-    } else if (q <= nt) {
-        A = E + r[1 + 2 * q];
-        len = r[2 + 2 * q];
-    } else {
-        return false;
-    }
-    return true;
-}
-
-// hash of run q of record block b (~0: no run / not a record block)
-static __global__ void k_run_hash(int nb, long E, const int *__restrict__ tok,
-                                  const int *__restrict__ trec, const unsigned short *__restrict__ d2,
-                                  unsigned long long *__restrict__ h) {
-    const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= (long)nb * kPrec) return;
-    const int b = (int)(id / kPrec), q = (int)(id - (long)b * kPrec);
-    unsigned long long x = ~0ull;
-    long A;
-    int len;
-    if (tok[b] == 2 && rec_run(trec + (long)b * kTileRec, E, q, A, len)) {
-        x = 0x9e3779b97f4a7c15ull * (unsigned long long)((A & 7) + 1) ^ (unsigned long long)len << 20;
-        for (int i = 0; i < len; i++) {
-            x ^= d2[A + i] + 0x9e3779b97f4a7c15ull + (x << 6) + (x >> 2);
-            x *= 0xbf58476d1ce4e5b9ull;
-        }
-        if (x == ~0ull) x = 0;
-    }
-    h[id] = x;
-}
-
-// every run's slots equal those of its pattern's representative (else *bad)
-static __global__ void k_run_verify(int nb, long E, const int *__restrict__ tok,
-                                    const int *__restrict__ trec,
-                                    const unsigned short *__restrict__ d2,
-                                    const long long *__restrict__ repA, int *__restrict__ bad) {
-    const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= (long)nb * kPrec) return;
-    const int b = (int)(id / kPrec), q = (int)(id - (long)b * kPrec);
-    long A;
-    int len;
-    if (tok[b] != 2 || !rec_run(trec + (long)b * kTileRec, E, q, A, len)) return;
-    const long R = repA[id];
-    bool ok = R >= 0 && (R & 7) == (A & 7);
-    for (int i = 0; ok && i < len; i++) ok = d2[A + i] == d2[R + i];
-    if (!ok) atomicAdd(bad, 1);
-}
-
-// deg8[v] = the vertex's CSR entries (clamped; blocks with a larger one are
-// not tiled)
-static __global__ void k_tile_deg(int V, const int *__restrict__ ptr,
-                                  unsigned char *__restrict__ deg8) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < V) deg8[v] = (unsigned char)min(ptr[v + 1] - ptr[v], 255);
-}
-
-// ------------------------------------------------ split incidence setup --
-// counts edges out of u order or with a u end outside [0, V)
-static __global__ void k_u_order_check(long E, int V, const int *__restrict__ Eu,
-                                unsigned long long *__restrict__ bad) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const int u = Eu[e];
-    if (u < 0 || u >= V || (e + 1 < E && u > Eu[e + 1])) atomicAdd(bad, 1ull);
-}
-
-// uptr[v] = first edge whose u end is >= v, v in [0, V] (Eu sorted)
-static __global__ void k_uptr(long E, int V, const int *__restrict__ Eu, int *__restrict__ uptr) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e > E) return;
-    const int lo = e == 0 ? 0 : Eu[e - 1] + 1;
-    const int hi = e == E ? V : Eu[e];
-    for (int v = lo; v <= hi; v++) uptr[v] = (int)e;
-}
-
-// One lane per vertex: code (bit i: the i-th CSR entry is the vertex's next
-// own u-run contribution; terminator bit at the degree) and the other
-// entries' addresses in CSR order.  blkok[b] = 1 when every vertex of block
-// b has <= 31 entries with its u-run in edge order, and the block's runs
-// fit the LDS halves (cap).
-static __global__ __launch_bounds__(256) void k_split_build(int V, long E, const int *__restrict__ ptr,
-                                                     const unsigned *__restrict__ idx,
-                                                     const int *__restrict__ uptr, long ototal,
-                                                     unsigned *__restrict__ mask,
-                                                     unsigned *__restrict__ oidx,
-                                                     int *__restrict__ blkok, int cap) {
-    const int v0 = blockIdx.x * kBlock;
-    const int v = v0 + threadIdx.x;
-    int ok = 1;
-    if (v < V) {
-        const int p0 = ptr[v], p1 = ptr[v + 1], u0 = uptr[v], u1 = uptr[v + 1];
-        const long o0 = (long)p0 - u0;
-        unsigned m = 0u;
-        int cu = 0, co = 0;
-        if (p1 - p0 > 31) ok = 0;
-        for (int j = p0; j < p1; j++) {
-            const unsigned id = idx[j];
-            if ((long)id < E) {
-                if ((long)id != (long)u0 + cu) ok = 0;
-                if (j - p0 < 32) m |= 1u << (j - p0);
-                cu++;
-            } else {
-                if (o0 + co >= 0 && o0 + co < ototal) oidx[o0 + co] = id;
-                co++;
-            }
-        }
-        if (cu != u1 - u0) ok = 0;
-        mask[v] = (p1 - p0 <= 31) ? (m | (1u << (p1 - p0))) : 0u;
-    }
-    const int all = __syncthreads_and(ok);
-    if (threadIdx.x == 0) {
-        const int vend = min(v0 + kBlock, V);
-        const int nu = uptr[vend] - uptr[v0];
-        const int no = (ptr[vend] - uptr[vend]) - (ptr[v0] - uptr[v0]);
-        blkok[blockIdx.x] = (all && nu <= cap && no >= 0 && no <= cap) ? 1 : 0;
-    }
 }
 
 // ====================================================================== //
@@ -1848,8 +1522,8 @@ __global__ __launch_bounds__(256) void k_edge_sweep(
 // Edge sweep of a tile-ordered graph (see tile_sum): sorted by u block, so
 // the u ends of a block's edges lie in a few consecutive u blocks, and
 // inside a (u block, v block) tile every v end lies in one 256-vertex block.
-// Each workgroup reads a 192-byte record of its edges (erec, built at
-// setup, scalar loads): the first u block, how many it spans and where in
+// Each workgroup reads a 192-byte record of its edges (erec, pfdr_layout.hpp,
+// scalar loads): the first u block, how many it spans and where in
 // the block each further u block starts, and the runs of equal v block
 // (start, v block base) -- at most kEbRuns; positions are relative to the
 // block's first edge, so every lookup is a 32-bit compare against scalars
@@ -1863,13 +1537,6 @@ __global__ __launch_bounds__(256) void k_edge_sweep(
 // vertex sweep.
 // u range staged: at most 16 KB of LDS (f64 blocks cover 512 edges)
 template <typename real> struct TlBlocks { static constexpr int v = 16384 / (2 * 256 * sizeof(R2<real>)) ; };
-constexpr int kEbRuns = 20;  // v-block runs in an edge block's record
-constexpr int kErecU = 4;    // rec[4]: staged span; rec[4 + q]: start of u block ub0 + q
-                             // (q = 1..3; INT_MAX if q >= nub)
-constexpr int kErecS = 8;    // rec[kErecS + 2r]: start of run r (INT_MAX if r >= nruns), + 1: its v base
-// rec[0..3]: ub0, nub, nruns (0: read Ev), uoff (smallest u end - ub0 * 256);
-// the staged u range is [ub0 * 256 + uoff, + span), span = largest - smallest + 1
-constexpr int kErec = kErecS + 2 * kEbRuns;
 // UNI: one weight La_d1 for every edge (la0) and no A1 (before any
 // reconditioning): a_e = cw * la0 is one value, computed once per lane.
 // RAT (UNI, Z-direct): each end's ratio (cw * la0 / Aux) / Ga comes formed
@@ -2122,86 +1789,6 @@ __global__ __launch_bounds__(256) void k_edge_sweep_tl(
     blk += b0;  // edge blocks [b0, b0 + nb) of this launch
     tl_gather<real, UNI, RAT>(E, V, Eu, luv, erec + (long)blk * kErec, Ev, xp, Z2, A1, cw, gi,
                               La_d1, la0, wz, rho, blk, s_xp, s_gi, rr);
-}
-
-// luv[p] = (Eu[p] mod 256) | (Ev[p] mod 256) << 8: both ends within their blocks
-static __global__ void k_tile_luv(long E, const int *__restrict__ Eu, const int *__restrict__ Ev,
-                                  unsigned short *__restrict__ luv) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < E) luv[p] = (unsigned short)((Eu[p] % kBlock) | ((Ev[p] % kBlock) << 8));
-}
-
-// nub of a block whose u blocks are not nondecreasing: never staged
-constexpr int kErecNoStage = 1 << 30;
-
-// the record of every edge block of k_edge_sweep_tl (EB edges; one wave per
-// block): first u block, span and the smallest / largest u end, where each
-// further u block starts, then the runs of equal v block in edge order
-// (nruns = 0 when there are more than kEbRuns: the block reads Ev); starts
-// relative to the block's first edge, padded past the last run.  Blocks
-// [b0, nblk).  Only the block's own record is written.
-//
-// A partitioned rank's edge block that straddles its interior / boundary cut
-// (the edges with a ghost end are sorted after the interior ones, each part
-// by u block) sees the u block DROP inside the block.  Its u ends are not a
-// few consecutive blocks from ub0 on, so the block is marked unstaged (nub =
-// kErecNoStage: k_edge_sweep_tl reads Eu) and no u-block start is recorded
-// -- u blocks below ub0 would otherwise index before the record.
-static __global__ void k_tile_erec(long E, int EB, int b0, int nblk, const int *__restrict__ Eu,
-                                   const int *__restrict__ Ev, int *__restrict__ erec) {
-    const int blk = b0 + blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-    const int lane = threadIdx.x & (kWave - 1);
-    if (blk >= nblk) return;  // whole wave
-    const long eb = (long)blk * EB, ee = min(eb + EB, E);
-    int *r = erec + (long)blk * kErec;
-    const int ub0 = Eu[eb] / kBlock;
-    bool drop = false;
-    for (long p = eb + 1 + lane; p < ee; p += kWave) drop |= Eu[p] / kBlock < Eu[p - 1] / kBlock;
-    drop = __ballot(drop) != 0;  // wave-uniform
-    int count = 0, umin = 0x7fffffff, umax = -1;
-    for (long c = eb; c < ee; c += kWave) {
-        const long p = c + lane;
-        bool st = false;
-        int vb = 0;
-        if (p < ee) {
-            vb = Ev[p] / kBlock;
-            st = p == eb || Ev[p - 1] / kBlock != vb;
-            const int u = Eu[p];
-            umin = min(umin, u);
-            umax = max(umax, u);
-            // u blocks ub0 + q starting here (edges sorted by u block: q1 >= q0 >= 0)
-            const int q1 = u / kBlock - ub0;
-            const int q0 = p == eb ? q1 : Eu[p - 1] / kBlock - ub0;
-            if (!drop)
-                for (int q = q0 + 1; q <= q1 && q < kErecS - kErecU; q++)
-                    r[kErecU + q] = (int)(p - eb);
-        }
-        const unsigned long long m = __ballot(st);
-        const int k = count + __popcll(m & ((1ull << lane) - 1));
-        if (st && k < kEbRuns) {
-            r[kErecS + 2 * k] = (int)(p - eb);
-            r[kErecS + 2 * k + 1] = vb * kBlock;
-        }
-        count += __popcll(m);
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        umin = min(umin, __shfl_xor(umin, o, kWave));
-        umax = max(umax, __shfl_xor(umax, o, kWave));
-    }
-    const int nub = drop ? kErecNoStage : Eu[ee - 1] / kBlock - ub0 + 1;
-    for (int k = count + lane; k < kEbRuns; k += kWave) {  // padding: never reached
-        r[kErecS + 2 * k] = 0x7fffffff;
-        r[kErecS + 2 * k + 1] = 0;
-    }
-    if (lane == 0) {
-        r[0] = ub0;
-        r[1] = nub;
-        r[2] = count <= kEbRuns ? count : 0;
-        r[3] = umin - ub0 * kBlock;
-        r[kErecU] = umax - umin + 1;
-        for (int q = drop ? 1 : max(nub, 1); q < kErecS - kErecU; q++) r[kErecU + q] = 0x7fffffff;
-    }
 }
 
 // Edge sweep of a graph whose edges are sorted by their u end (uptr: first
@@ -2615,15 +2202,6 @@ __global__ __launch_bounds__(256, 7) void k_vertex_sweep_pair(VArgs<real> a, int
             a.part[2 * b0 + 3] = d1;
         }
     }
-}
-
-// entries of each record block's list (0 for the others): the pair sweep's
-// LDS list per block is the largest
-static __global__ void k_rec_entries(int V, int nb, const int *__restrict__ ptr,
-                                     const int *__restrict__ tok, int *__restrict__ out) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    out[b] = tok[b] == 2 ? ptr[min((b + 1) * kBlock, V)] - ptr[b * kBlock] : 0;
 }
 
 // Vertex sweep of a small graph (the fused-decision range) whose edge sweep

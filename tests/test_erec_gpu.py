@@ -1,5 +1,5 @@
 """GPU: the edge-block records of the tiled edge sweep (k_tile_erec,
-csrc/pfdr_quadratic_kernels.hpp) on a partitioned rank's edge order, checked
+csrc/pfdr_layout.hip; format: csrc/pfdr_layout.hpp) on a partitioned rank's edge order, checked
 deterministically through the C-ABI test hook pfdr_debug_tile_erec.
 
 A partitioned rank sorts its edges by (u block, v block) with the edges that
@@ -39,7 +39,7 @@ def _hook(lib, Eu, Ev, dtype_code, b0, nb, rec):
 
 
 def erec_host(Eu, Ev, blk, EB, KEREC, RUNS, NOSTAGE):
-    """the record k_tile_erec writes for edge block blk (see its comment)"""
+    """the record k_tile_erec writes for edge block blk (csrc/pfdr_layout.hpp)"""
     eb, ee = blk * EB, min(blk * EB + EB, Eu.size)
     u, v = Eu[eb:ee].astype(np.int64), Ev[eb:ee].astype(np.int64)
     ub, vb = u // 256, v // 256

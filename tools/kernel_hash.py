@@ -17,8 +17,8 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 COMMON = ("pfdr_dev.hpp", "pfdr_graph.hip", "pfdr_graph.hpp", "pfdr_halo.hpp",
           "pfdr_monosum.hip", "pfdr_monosum.hpp", "pfdr_session.hpp")
 SOURCES = {
-    "quadratic": COMMON + ("pfdr_order.hip", "pfdr_order.hpp", "pfdr_quadratic.hip",
-                           "pfdr_quadratic_kernels.hpp"),
+    "quadratic": COMMON + ("pfdr_layout.hip", "pfdr_layout.hpp", "pfdr_order.hip",
+                           "pfdr_order.hpp", "pfdr_quadratic.hip", "pfdr_quadratic_kernels.hpp"),
     "simplex": COMMON + ("pfdr_simplex.hip",),
 }
 
