@@ -6,6 +6,7 @@
 #include <cstring>
 #include <stdexcept>
 
+#include "pfdr_batch.hpp"
 #include "pfdr_loop.hpp"
 #include "pfdr_order.hpp"
 #include "pfdr_quadratic_kernels.hpp"
@@ -48,10 +49,12 @@ __global__ void k_edge_relabel(long E, const unsigned *__restrict__ eorig,
 }
 
 template <typename real>
-class QuadSession final : public IterLoop<real> {
+class QuadSession final : public IterLoop<real>, public DenseLane<real> {
   public:
+    // share: the session is a lane of a batch (pfdr_batch.hpp) on that
+    // batch's matrix
     explicit QuadSession(const pfdr_problem *p, const pfdr_csc *csc = nullptr,
-                         bool reusable = false);
+                         bool reusable = false, const LaneShare<real> *share = nullptr);
     void reload(const pfdr_reload *r) override;
     ~QuadSession() override {
         this->close();  // (the loop's streams are drained before any buffer goes)
@@ -60,6 +63,32 @@ class QuadSession final : public IterLoop<real> {
     }
     void result(void *X_host, int *it, void *Obj_host, void *Dif_host) override;
     void *device_x() override;
+    // the seams a batch drives its lanes through (DenseLane)
+    SessionBase &base() override { return *this; }
+    LaneFacts facts() const override {
+        return LaneFacts{V_, mode_ == A_DIRECT ? N_ : V_, mode_ == A_DIRECT, exact_, symv_,
+                         gated(), rec_obj_, rows_nb_, rows_cpb_, snb_};
+    }
+    LaneView<real> view() override {
+        return LaneView<real>{xp_.p, R_.p, Y_.p, Ga_.p, gated() ? ctrl_.p : nullptr, Rpart_.p,
+                              xfull_.p, spart_.p};
+    }
+    const real *diag() const override { return diag_.p; }
+    void lane_head() override { head(); }
+    void lane_forward() override { forward_dense(gated() ? GATE_ACTIVE : GATE_NONE); }
+    void lane_objective() override { objective(); }
+    // the chunk boundary of a lane, whose bodies the batch launches in lock
+    // step with the other lanes': the control block into the mirror (the batch
+    // waits once for all its lanes), then what IterLoop::run does after a
+    // chunk of n bodies (its bookkeeping and settle(), restated here)
+    void lane_chunk_begin() override { it0_ = it_; }
+    void lane_snapshot() override {
+        PFDR_HIP(hipMemcpyAsync(hctrl_, ctrl_.p, sizeof(Ctrl<real>), hipMemcpyDeviceToHost, stream));
+    }
+    void lane_settle(int n) override;
+    int lane_it() const override { return it_; }
+    int lane_itmax() const override { return itMax_; }
+    bool lane_stopped() const override { return stopped_; }
 
   private:
     using L = IterLoop<real>;
@@ -169,6 +198,17 @@ class QuadSession final : public IterLoop<real> {
     DevBuf<real> La_d1_, La_l1_, Y_, A_, L_;
     DevBuf<R2<real>> xp_;
     DevBuf<real> diag_, Ga_, invAux_, Th_l1_, absval_, grad_, pre_, xout_;
+    // a lane of a batch borrows A_ and, past the first lane, diag_ (their n
+    // stays 0: the owner counts them).  Declared after them, so destroyed
+    // before them -- also when the constructor throws: a borrowed pointer is
+    // dropped, never freed here
+    struct Borrowed {
+        DevBuf<real> *a = nullptr, *d = nullptr;
+        ~Borrowed() {
+            if (a) a->p = nullptr;
+            if (d) d->p = nullptr;
+        }
+    } borrowed_;
     DevBuf<real> Z2_, wz_;
     // splitting weights as factors (k_d1_weights): a_e = cw_ La_d1[e] until the
     // first reconditioning, then A1_[e]; (Ga, invAux) pairs of every vertex
@@ -205,6 +245,7 @@ class QuadSession final : public IterLoop<real> {
     void forward_dense(int gate);
     void gradient();
     void objective();
+    void head();  // the sweeps and the loop decision of one iteration (not fused)
     void body(int i, int n) override;
     void recondition() override;
     void print_progress() override;
@@ -291,8 +332,9 @@ class QuadSession final : public IterLoop<real> {
     bool sparse_ = false;
     SparseOp<real> sp_;
     // Sessions whose products run in the reference's order (exact_, or a
-    // sparse A on its sequential kernels; direct mode, weights >= 0) sum the
-    // recorded objective in that order too (k_obj_terms, three mono_sum's):
+    // sparse A on its sequential kernels; weights >= 0) sum the recorded
+    // objective in that order too (k_obj_terms, three mono_sum's; in A^tA
+    // mode the data term, whose terms change sign, through k_obj_data_seq):
     // Obj is then the reference's, bit for bit, like X, it and Dif.
     // oterms_ = the terms of the N rows, E edges (caller's edge order: a
     // tiled session keeps emap_, its edge positions, for it) and V vertices,
@@ -311,13 +353,14 @@ class QuadSession final : public IterLoop<real> {
     }
   private:
     DevBuf<real> spart_;
-    void plan_symv();
+    void plan_symv(int known);
     template <int EPI> void ata_product(ColArgs<real> ca);
 };
 
 // ----------------------------------------------------------------- setup --
 template <typename real>
-QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool reusable_session) {
+QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool reusable_session,
+                               const LaneShare<real> *share) {
     if (p->V <= 0 || p->E < 0) throw std::runtime_error("V must be > 0 and E >= 0");
     if (!p->X || !p->Y || !p->Eu || !p->Ev || !p->La_d1)
         throw std::runtime_error("X, Y, Eu, Ev and La_d1 are required");
@@ -407,7 +450,11 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool 
     // the matrix and what depends on it alone: kept by a reload
     const size_t asz = sparse_ ? 0 : mode_ == A_DIRECT ? (size_t)N_ * V
                      : mode_ == A_ATA ? (size_t)Vglob_ * V : mode_ == A_DIAG ? V : 0;
-    copy_in(A_, p->A, asz, mem, s, pins_);
+    if (share) {  // (a lane: the batch holds and counts the matrix)
+        A_.p = const_cast<real *>(share->A);
+        borrowed_.a = &A_;
+    }
+    else copy_in(A_, p->A, asz, mem, s, pins_);
     if (sparse_) {  // checked copy of the CSC, CSR view, kernel family
         sp_.setup(V_, N_, csc, mem, kExactChain, s, pins_);
         sparse_exact = sp_.exact ? 1 : 0;
@@ -437,7 +484,13 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool 
     Z2_.alloc(2 * En + (halo_ ? (size_t)halo_->R : 0) + kSlotGroup);
     gi_.alloc(Vg + 2);
     PFDR_HIP(hipMemsetAsync(gi_.p, 0, (Vg + 2) * sizeof(R2<real>), s));
-    diag_.alloc(V); Ga_.alloc(Vg); invAux_.alloc(Vg); absval_.alloc(V);
+    if (share && share->diag) {
+        diag_.p = const_cast<real *>(share->diag);
+        borrowed_.d = &diag_;
+    } else {
+        diag_.alloc(V);
+    }
+    Ga_.alloc(Vg); invAux_.alloc(Vg); absval_.alloc(V);
     if (flavour_ == 0 && p->La_l1) Th_l1_.alloc(V);
     nbv_ = grid_for(V);
     nbe_ = grid_for(E);
@@ -460,13 +513,18 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool 
         rows_nb_ = (V_ + rows_cpb_ - 1) / rows_cpb_;
         if (!sparse_) Rpart_.alloc((size_t)rows_nb_ * N_);
     }
-    if (mode_ == A_ATA) { pre_.alloc(V); xout_.alloc(V); xfull_.alloc(Vglob_); plan_symv(); }
+    if (mode_ == A_ATA) {
+        pre_.alloc(V); xout_.alloc(V); xfull_.alloc(Vglob_);
+        plan_symv(share ? share->symv : -1);
+    }
     if (mode_ == A_DIRECT && halo_) Rsum_.alloc(N_);
 
     this->alloc_ctrl();
 
     // diagonal of A^t A
-    if (mode_ == A_DIRECT) {
+    if (borrowed_.d) {
+        // (a lane: the first lane's)
+    } else if (mode_ == A_DIRECT) {
         ColArgs<real> ca{};
         ca.A = A_.p; ca.ncols = V_; ca.len = N_; ca.out = diag_.p;
         // (a sparse session's two setup products are always timed: profiling
@@ -530,8 +588,9 @@ QuadSession<real>::QuadSession(const pfdr_problem *p, const pfdr_csc *csc, bool 
         capturable_ = halo_->tr->capturable() && !rec_obj_;
         graphs_ok_ = itMax_ >= 2 * chunk_ && capturable_;
     } else if (!tiny_) {
-        capturable_ = true;
-        graphs_ok_ = itMax_ >= 2 * chunk_;
+        // (a lane's bodies are launched by its batch, in lock step: no graph)
+        capturable_ = !share;
+        graphs_ok_ = capturable_ && itMax_ >= 2 * chunk_;
         // (an edgeless graph has no edge sweep to carry the decision)
         fuse_ = track_ && !rec_obj_ && (mode_ == A_IDENT || mode_ == A_DIAG) &&
                 nbv_ <= kFuseBlocks && E_ > 0 && !want_seq;
@@ -722,12 +781,13 @@ void QuadSession<real>::load_values(const Values &in) {
     }
     int hf[4] = {1, 1, 1, 1};
     seqobj_ = false;
-    if (rec_obj_ && mode_ == A_DIRECT && !halo_ && (exact_ || (sparse_ && sp_.exact))) {
+    if (rec_obj_ && !halo_ &&
+        ((mode_ == A_DIRECT && (exact_ || (sparse_ && sp_.exact))) || (mode_ == A_ATA && exact_))) {
         PFDR_HIP(hipMemcpyAsync(hf, flags_.p, sizeof(hf), hipMemcpyDeviceToHost, s));
         PFDR_HIP(hipStreamSynchronize(s));
         seqobj_ = !hf[VF_D1_NEG] && !hf[VF_L1_NEG];
         if (seqobj_ && !oterms_.p) {
-            ot_e_ = ((long)N_ + 3) / 4 * 4;
+            ot_e_ = mode_ == A_DIRECT ? ((long)N_ + 3) / 4 * 4 : 0;  // (A^tA: no row terms)
             ot_v_ = ot_e_ + (E_ + 3) / 4 * 4;
             oterms_.alloc((size_t)ot_v_ + V);
             ows_.alloc(mono_ws_bytes<real>(std::max<long>(std::max<long>(N_, E_), V_)));
@@ -1054,11 +1114,19 @@ void QuadSession<real>::col_product(ColArgs<real> ca) {
 // (k_sym_check, one pass at setup; a matrix that is not keeps the column
 // dots, which read it as given)
 template <typename real>
-void QuadSession<real>::plan_symv() {
+void QuadSession<real>::plan_symv(int known) {
     using S = SymT<real>;
     if (halo_ || exact_ || V_ < 4 * S::T) return;
     if (V_ % S::VW || ((uintptr_t)A_.p % 16)) return;
     hipStream_t s = stream;
+    if (known >= 0) {  // (a lane: the first lane's verdict on the shared matrix)
+        if (!known) return;
+        symv_ = true;
+        snb_ = (V_ + S::T - 1) / S::T;
+        spart_.alloc((size_t)snb_ * V_);
+        symv = 1;
+        return;
+    }
     DevBuf<int> flag(1);
     PFDR_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), s));
     const long n64 = (V_ + 63) / 64;
@@ -1209,18 +1277,30 @@ void QuadSession<real>::objective() {
     const Ctrl<real> *c = ctrl_.p;
     if (seqobj_) {  // the three sums term by term, as the reference adds them
         real *tn = oterms_.p, *te = oterms_.p + ot_e_, *tv = oterms_.p + ot_v_;
-        const long nmax = std::max<long>(std::max<long>(N_, E_), V_);
+        const bool direct = mode_ == A_DIRECT;
+        const int nrow = direct ? N_ : 0;
+        if (!direct) {  // (A^tA X) in the reference's order (exact_: k_col_seq)
+            ColArgs<real> ca{};
+            ca.out = pre_.p;
+            ca.ctrl = c; ca.gate = GATE_OBJ;
+            ca.w = full_x();
+            ata_product<EPI_STORE>(ca);
+        }
+        const long nmax = std::max<long>(std::max<long>(nrow, E_), V_);
         k_obj_terms<real><<<grid_for(nmax), kBlock, 0, s>>>(
-            N_, E_, V_, R_.p, Eu_.p, Ev_.p, oemap(), xp_.p, La_d1_.p,
+            nrow, E_, V_, R_.p, Eu_.p, Ev_.p, oemap(), xp_.p, La_d1_.p,
             flavour_ == 0 ? La_l1_.p : nullptr, tn, te, tv, c);
         PFDR_HIP(hipGetLastError());
         PFDR_HIP(hipMemsetAsync(red_.p, 0, 3 * sizeof(real), s));
-        mono_sum<real>(N_, tn, nullptr, 0, nullptr, red_.p, nullptr, ows_.p, s);
+        if (direct)
+            mono_sum<real>(N_, tn, nullptr, 0, nullptr, red_.p, nullptr, ows_.p, s);
+        else
+            k_obj_data_seq<real><<<1, kBlock, 0, s>>>(V_, xp_.p, pre_.p, Y_.p, red_.p, c);
         if (E_) mono_sum<real>(E_, te, nullptr, 0, nullptr, red_.p + 2, nullptr, ows_.p, s);
         if (flavour_ == 0 && La_l1_.p)
             mono_sum<real>(V_, tv, nullptr, 0, nullptr, red_.p + 1, nullptr, ows_.p, s);
-        k_obj_write<real><<<1, 64, 0, s>>>(red_.p, 1, flavour_ == 0 && La_l1_.p != nullptr,
-                                           ctrl_.p, Obj_.p);
+        k_obj_write<real><<<1, 64, 0, s>>>(red_.p, direct ? 1 : 0,
+                                           flavour_ == 0 && La_l1_.p != nullptr, ctrl_.p, Obj_.p);
         PFDR_HIP(hipGetLastError());
         return;
     }
@@ -1447,7 +1527,6 @@ template <typename real>
 void QuadSession<real>::body(int i, int n) {
     hipStream_t s = stream;
     const bool gated = track_ || rec_obj_;
-    const Ctrl<real> *c = gated ? ctrl_.p : nullptr;
     if (fuse_) {
         // E(i) decides iteration i - 1 (from cb[(i-1)&1] into cb[i&1]), V(i)
         // reads cb[i&1]; the last body closes the chunk with k_reduce_decide's
@@ -1468,6 +1547,43 @@ void QuadSession<real>::body(int i, int n) {
         PFDR_HIP(hipGetLastError());
         return;
     }
+    head();
+    if (mode_ == A_DIRECT || mode_ == A_ATA) forward_dense(gated ? GATE_ACTIVE : GATE_NONE);
+    if (rec_obj_) objective();
+}
+
+template <typename real>
+void QuadSession<real>::lane_settle(int n) {
+    const bool g = gated();
+    if (g) {
+        it_ = hctrl_->it;
+    } else {
+        it_ += n;
+        if (it_ >= itMax_) stopped_ = true;
+    }
+    if (g && hctrl_->stop) {
+        stopped_ = true;
+    } else if (g && hctrl_->recond) {
+        recondition();
+        reconditionings++;
+        hctrl_->recond = 0;
+        hctrl_->halt = 0;
+        push_ctrl();
+        if (verbose_) { printf("done.\n"); fflush(stdout); }
+    }
+    if (verbose_ && (it_ >= next_print_ || stopped_)) {
+        print_progress();
+        next_print_ = it_ + verbose_;
+    }
+}
+
+// the sweeps of one iteration and the loop decision on it (every variant but
+// the fused one, whose decision rides in the next edge sweep)
+template <typename real>
+void QuadSession<real>::head() {
+    hipStream_t s = stream;
+    const bool gated = track_ || rec_obj_;
+    const Ctrl<real> *c = gated ? ctrl_.p : nullptr;
     sweeps(c);
     if (seqdif_) {
         // the reference's two sequential sums (ref :518-526), then its decision
@@ -1485,8 +1601,6 @@ void QuadSession<real>::body(int i, int n) {
         k_decide<real><<<1, 64, 0, s>>>(ctrl_.p, red_.p, rec_dif_ ? Dif_.p : nullptr, track_ ? 1 : 0);
     }
     PFDR_HIP(hipGetLastError());
-    if (mode_ == A_DIRECT || mode_ == A_ATA) forward_dense(gated ? GATE_ACTIVE : GATE_NONE);
-    if (rec_obj_) objective();
 }
 
 // red_[0..2) = the sums of (X_ - X)^2 and X^2 over every vertex in the
@@ -1613,6 +1727,16 @@ SessionBase *create_quadratic_session_reusable(const pfdr_problem *p, const pfdr
     if (p->dtype == PFDR_F64) return new QuadSession<double>(p, A, true);
     throw std::runtime_error("dtype must be PFDR_F32 or PFDR_F64");
 }
+
+// a lane of a batch: a reusable session on the batch's matrix
+template <typename real>
+DenseLane<real> *create_quadratic_lane(const pfdr_problem *p, const LaneShare<real> &share) {
+    return new QuadSession<real>(p, nullptr, true, &share);
+}
+template DenseLane<float> *create_quadratic_lane<float>(const pfdr_problem *,
+                                                        const LaneShare<float> &);
+template DenseLane<double> *create_quadratic_lane<double>(const pfdr_problem *,
+                                                          const LaneShare<double> &);
 
 SessionBase *create_quadratic_session_sparse(const pfdr_problem *p, const pfdr_csc *A) {
     if (!A) throw std::runtime_error("sparse A: null matrix");

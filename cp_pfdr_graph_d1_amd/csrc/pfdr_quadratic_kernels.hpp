@@ -2660,6 +2660,34 @@ __global__ __launch_bounds__(256) void k_obj_terms(
     }
 }
 
+// The A^tA objective's data term in the reference's order (ref :387-401: one
+// accumulator over v of X[v] (1/2 (A^tA X)[v] - A^tY[v])): the terms change
+// sign, so no mono_sum; one workgroup stages them through LDS and its first
+// lane adds them left to right (ordered_add).  Small problems only (the
+// sequential-order path, V <= 8192).  out[0] = the sum.
+template <typename real>
+__global__ __launch_bounds__(256) void k_obj_data_seq(int V, const R2<real> *__restrict__ xp,
+                                                      const real *__restrict__ papp,
+                                                      const real *__restrict__ Y,
+                                                      real *__restrict__ out,
+                                                      const Ctrl<real> *ctrl) {
+    if (gated(ctrl, GATE_OBJ)) return;
+    constexpr int CH = 4096;
+    __shared__ __attribute__((aligned(16))) real t[CH];
+    real s = real(0);
+    for (int v0 = 0; v0 < V; v0 += CH) {
+        const int m = min(CH, V - v0);
+        for (int i = threadIdx.x; i < m; i += kBlock) {
+            const real x = xp[v0 + i].x;
+            t[i] = x * (real(0.5) * papp[v0 + i] - Y[v0 + i]);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s = ordered_add<real>(s, t, m);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = s;
+}
+
 // objective partials -> red[0..2] = (data, l1, tv)
 template <typename real>
 __global__ __launch_bounds__(256) void k_obj_reduce(

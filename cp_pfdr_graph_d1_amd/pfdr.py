@@ -84,6 +84,8 @@ EXPORTED = (
     "pfdr_session_device_bytes", "pfdr_session_query", "pfdr_session_destroy",
     "pfdr_session_create_sparse", "pfdr_debug_session_csr",
     "pfdr_session_create_reusable", "pfdr_session_reload",
+    "pfdr_batch_create", "pfdr_batch_run", "pfdr_batch_result", "pfdr_batch_reload",
+    "pfdr_batch_query", "pfdr_batch_destroy",
     "pfdr_quadratic_d1_l1_csc_f32", "pfdr_quadratic_d1_l1_csc_f64",
     "pfdr_quadratic_d1_bounds_csc_f32", "pfdr_quadratic_d1_bounds_csc_f64",
     "pfdr_comm_unique_id", "pfdr_comm_init", "pfdr_comm_destroy",
@@ -280,6 +282,13 @@ def _is_device(a):
     return hasattr(a, "data_ptr")
 
 
+def _vp(a):
+    """a numpy array, an address or None as a void pointer"""
+    if a is None:
+        return None
+    return C.c_void_p(a.ctypes.data if isinstance(a, np.ndarray) else int(a))
+
+
 def _cp_stats(fill, first="n_cuts"):
     """the cut pursuits' seconds[6] / counts[4] record, which ``fill(seconds,
     counts)`` writes -> dict: seconds per phase and counts"""
@@ -399,6 +408,34 @@ class Lib:
 
     def __init__(self):
         self.lib = load()
+
+    # batched dense sessions (pfdr_batch_*): raw mirrors, addresses as
+    # integers or None, `problem` a Problem and `reload` a Reload
+    def batch_create(self, problem, B):
+        h = C.c_void_p()
+        _check(self.lib.pfdr_batch_create(C.byref(h), None if problem is None else
+                                          C.byref(problem), C.c_int(B)), "pfdr_batch_create")
+        return h
+
+    def batch_run(self, handle, iters, it=None):
+        _check(self.lib.pfdr_batch_run(handle, C.c_int(iters), _vp(it)), "pfdr_batch_run")
+
+    def batch_result(self, handle, X=None, it=None, Obj=None, Dif=None):
+        _check(self.lib.pfdr_batch_result(handle, _vp(X), _vp(it), _vp(Obj), _vp(Dif)),
+               "pfdr_batch_result")
+
+    def batch_reload(self, handle, reload):
+        _check(self.lib.pfdr_batch_reload(handle, None if reload is None else C.byref(reload)),
+               "pfdr_batch_reload")
+
+    def batch_query(self, handle, what):
+        v = C.c_int64(0)
+        _check(self.lib.pfdr_batch_query(handle, None if what is None else what.encode(),
+                                         C.byref(v)), "pfdr_batch_query")
+        return v.value
+
+    def batch_destroy(self, handle):
+        self.lib.pfdr_batch_destroy(handle)
 
     def quadratic_d1_l1(self, X0, Y, A, N, Eu, Ev, La_d1, La_l1=None,
                         positivity=0, Ltype=SCAL, L=None, rho=1.5,
@@ -1325,6 +1362,169 @@ class Session:
     def close(self):
         if getattr(self, "h", None):
             self.lib.pfdr_session_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchSession:
+    """B dense-A problems (kind l1 or bounds; direct, N > 0, or A^tA, N = -V)
+    that share A, the graph, the penalties and every scalar and differ in the
+    observation and the iterate, iterated in lock step: one pass over A serves
+    a group of channels (pfdr_batch_*, include/pfdr_mi355x.h).  ``X0`` is
+    (B, V) and ``Y`` is (B, len), len = N or V; ``B`` defaults to
+    ``Y.shape[0]``; the other keywords are Session's.  Channel b gives the
+    bytes of a Session on (X0[b], Y[b]).  Arrays are numpy, or torch GPU
+    tensors with ``device=True``."""
+
+    def __init__(self, kind, dtype, V, E, Eu, Ev, La_d1, X0, Y, N=0, A=None, B=None,
+                 La_l1=None, positivity=0, lo=-np.inf, hi=np.inf, Ltype=SCAL, L=None, rho=1.5,
+                 condMin=1e-3, difRcd=0.0, difTol=0.0, itMax=1000, record_obj=False,
+                 record_dif=False, verbose=0, device=False, reorder=REORDER_AUTO,
+                 evolution=EVOLUTION_AUTO, spec=SPEC_AUTO):
+        ct, _, dcode = _real(dtype)
+        self.dtype = np.dtype(dtype)
+        self.device = bool(device)
+        self._keep = []
+        V, E, N = int(V), int(E), int(N)
+        self.len = N if N > 0 else V
+        if B is None:
+            if getattr(Y, "ndim", 0) != 2:
+                raise PFDRError("BatchSession: Y must have shape (B, %d)" % self.len)
+            B = int(Y.shape[0])
+        B = int(B)
+        self.B, self.V = B, V
+        self._shape("X0", X0, (B, V), False)
+        self._shape("Y", Y, (B, self.len), False)
+        if A is not None:
+            if isinstance(A, CSC):
+                raise PFDRError("BatchSession: a sparse A is not offered (dense A only)")
+            self._shape("A", A, None, False, size=self.len * V)
+        self._shape("La_d1", La_d1, (E,), False)
+        self._shape("La_l1", La_l1, (V,), True)
+        self.lib = load()
+        if device:
+            _producers_done()
+        p = Problem()
+        p.kind, p.dtype = kind, dcode
+        p.mem = PFDR_MEM_DEVICE if device else PFDR_MEM_HOST
+        p.V, p.E, p.N = V, E, N
+        p.X, p.Y, p.A = self._addr(X0), self._addr(Y), self._addr(A)
+        p.Eu, p.Ev = self._addr(Eu, np.int32), self._addr(Ev, np.int32)
+        p.La_d1, p.La_l1, p.L = self._addr(La_d1), self._addr(La_l1), self._addr(L)
+        p.positivity, p.min, p.max = positivity, lo, hi
+        p.Ltype = Ltype
+        p.rho, p.condMin, p.difRcd, p.difTol = rho, condMin, difRcd, difTol
+        p.itMax, p.verbose = itMax, verbose
+        p.record_obj, p.record_dif = int(record_obj), int(record_dif)
+        p.reorder, p.evolution, p.spec = reorder, evolution, spec
+        self.problem = p
+        self.itMax = itMax
+        self.record_obj, self.record_dif = bool(record_obj), bool(record_dif)
+        self.h = None
+        self.h = Lib().batch_create(p, B)
+
+    def _shape(self, name, a, shape, optional, size=None):
+        """the shape and dtype of an input, before the library is called"""
+        if a is None:
+            if optional:
+                return
+            raise PFDRError("BatchSession: %s is required" % name)
+        if self.device != _is_device(a):
+            raise PFDRError("BatchSession: %s must be a %s (device=%s)" % (
+                name, "torch GPU tensor" if self.device else "numpy array", self.device))
+        got = tuple(a.shape)
+        if shape is not None and got != tuple(shape):
+            raise PFDRError("BatchSession: %s has shape %s, expected %s" % (name, got, shape))
+        if size is not None and int(np.prod(got)) != size:
+            raise PFDRError("BatchSession: %s has %d entries, expected %d" % (
+                name, int(np.prod(got)), size))
+        if self.device:
+            import torch
+            want = torch.float32 if self.dtype == np.float32 else torch.float64
+            if a.dtype != want or not a.is_contiguous():
+                raise PFDRError("BatchSession: %s must be a contiguous %s tensor" % (name, want))
+        elif np.asarray(a).dtype != self.dtype:
+            raise PFDRError("BatchSession: %s has dtype %s, expected %s" % (
+                name, np.asarray(a).dtype, self.dtype))
+
+    def _addr(self, a, dt=None, keep=None):
+        if a is None:
+            return None
+        keep = self._keep if keep is None else keep
+        if self.device:
+            keep.append(a)
+            return C.c_void_p(a.data_ptr())
+        # (A: column major, given flat or as an (N, V) Fortran-ordered array)
+        a = np.asarray(a)
+        if a.ndim == 2 and a.flags.f_contiguous and not a.flags.c_contiguous:
+            a = a.T
+        a = np.ascontiguousarray(a, dt or self.dtype)
+        keep.append(a)
+        return C.c_void_p(a.ctypes.data)
+
+    def run(self, iters):
+        """up to `iters` more iterations of every channel -> its (B,)"""
+        its = np.zeros(self.B, np.int32)
+        Lib().batch_run(self.h, int(iters), its)
+        return its
+
+    def result(self):
+        """-> X (B, V), it (B,), Obj, Dif: lists of per-channel arrays cut to
+        the channel's own it (Obj: it + 1 values), or None where not recorded"""
+        B, m = self.B, self.itMax
+        X = np.zeros((B, self.V), self.dtype)
+        its = np.zeros(B, np.int32)
+        Obj = np.zeros((B, m + 1), self.dtype) if self.record_obj else None
+        Dif = np.zeros(B * max(m, 0) + 1, self.dtype) if self.record_dif else None
+        Lib().batch_result(self.h, X, its, Obj, Dif)
+        if Obj is not None:
+            Obj = [Obj[b, :its[b] + 1].copy() for b in range(B)]
+        if Dif is not None:
+            Dif = [Dif[b * m:b * m + its[b]].copy() for b in range(B)]
+        return X, its, Obj, Dif
+
+    def reload(self, Y=None, X0=None, La_d1=None, La_l1=None, L=None, lo=None, hi=None,
+               rho=None, condMin=None, difRcd=None, difTol=None, itMax=None):
+        """pfdr_batch_reload: new values for every channel, back to iteration
+        0.  Y (B, len) and X0 (B, V) are per channel (None: kept; for X0 a warm
+        start of every channel from its own iterate); La_d1, La_l1 and L are
+        shared; None keeps a scalar."""
+        p = self.problem
+        self._shape("Y", Y, (self.B, self.len), True)
+        self._shape("X0", X0, (self.B, self.V), True)
+        self._shape("La_d1", La_d1, (p.E,), True)
+        self._shape("La_l1", La_l1, (self.V,), True)
+        if self.device:
+            _producers_done()
+        keep = []
+
+        def scalar(new, cur):
+            return cur if new is None else new
+
+        r = Reload()
+        r.mem = p.mem
+        r.X, r.Y = self._addr(X0, keep=keep), self._addr(Y, keep=keep)
+        r.La_d1, r.La_l1 = self._addr(La_d1, keep=keep), self._addr(La_l1, keep=keep)
+        r.L = self._addr(L, keep=keep)
+        r.min, r.max = scalar(lo, p.min), scalar(hi, p.max)
+        r.rho, r.condMin = scalar(rho, p.rho), scalar(condMin, p.condMin)
+        r.difRcd, r.difTol = scalar(difRcd, p.difRcd), scalar(difTol, p.difTol)
+        r.itMax = scalar(itMax, p.itMax)
+        Lib().batch_reload(self.h, r)
+        p.min, p.max, p.rho, p.condMin = r.min, r.max, r.rho, r.condMin
+        p.difRcd, p.difTol, p.itMax = r.difRcd, r.difTol, r.itMax
+
+    def query(self, what):
+        return Lib().batch_query(self.h, what)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.pfdr_batch_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -261,7 +261,9 @@ int64_t pfdr_session_device_bytes(pfdr_session *s);
  * (1: such a graph's contributions are stored in per-vertex-block lists, so
  * its vertex sweep stages them without dependent address loads),
  * "dense_exact" (1: the dense products run in the reference's sequential
- * order, bit-exact; small single-GPU problems), "tiled_blocks" (vertex
+ * order, bit-exact; small single-GPU problems; with weights >= 0 a recorded
+ * Obj is added in that order as well, in direct and in A^tA mode),
+ * "tiled_blocks" (vertex
  * blocks staging tile-ordered contributions) and "record_blocks" (of those,
  * the blocks whose runs fit one per-block record), "slot_patterns" (distinct
  * slot sequences of those records' runs, 0: per-entry slots), "speculative"
@@ -396,6 +398,64 @@ typedef struct pfdr_reload {
 } pfdr_reload;
 int pfdr_session_create_reusable(pfdr_session **out, const pfdr_problem *p, const pfdr_csc *A);
 int pfdr_session_reload(pfdr_session *s, const pfdr_reload *r);
+
+/* ------------------------------------------------ batched dense sessions -- */
+/* B problems of kind l1 or bounds with a dense A (direct, N > 0, or
+ * premultiplied, N = -V) that share A, the graph, La_d1, La_l1, L, the bounds
+ * and every scalar, and differ in the observation and in the iterate -- a time
+ * series of sensor vectors through one lead field.  The iterations of the
+ * dense modes are the stream of A; a batch iterates its channels in lock step
+ * and one pass over A serves a group of G channels ("channel_group", 8), so B
+ * channels cost ceil(B / G) passes per product, not B.
+ *
+ * Layout: every array is channel-major and contiguous.  p->X is B x V
+ * (channel b at X + b V), p->Y is B x len (len = N in direct mode, V in A^tA
+ * mode); the outputs X (B x V), it (B), Obj (B x (itMax + 1)) and Dif (B x
+ * itMax, itMax the creation's) follow the same rule; any output may be NULL.
+ * mem covers all arrays, as for a session.  1 <= B <= 64.  A is copied to the
+ * device once.
+ *
+ * Channel equality: channel b is the session pfdr_session_create would make
+ * on (X_b, Y_b, the shared rest); after any sequence of pfdr_batch_run calls
+ * its X, it, Obj and Dif are that session's bytes after the same sequence of
+ * pfdr_session_run calls -- in f32 and f64, on every product path (the
+ * sequential-order one of small problems, "dense_exact", the column dots,
+ * the row partials, the symmetric tiles, "symv"), with difTol > 0 (each
+ * channel stops at its own iteration and is not written again while the
+ * others go on) and with difRcd > 0 (each channel reconditions at its own
+ * iterations and decays its own difRcd^2).  The batched kernels add every
+ * (row or column, channel) sum in the order and precision of the scalar
+ * kernel they replace.  On the sequential-order path the products stay the
+ * scalar kernels, one launch per channel.
+ *
+ * pfdr_batch_run returns when every channel has stopped or has run `iters`
+ * more iterations; it[b] (it may be NULL) is channel b's total.
+ * pfdr_batch_reload is pfdr_session_reload for every channel at once: r->Y
+ * (B x len) and r->X (B x V) are per channel, NULL Y keeps the current
+ * observations and NULL X warm-starts every channel from its own iterate;
+ * La_d1, La_l1 and L are one shared array each, or NULL; the scalars are read
+ * and the refusals are those of pfdr_session_reload (the batch stays
+ * runnable).  What follows equals a fresh batch on the new values, byte for
+ * byte; A, diag(A^tA), the symmetric-product plan and the graph tables are
+ * kept.  pfdr_batch_query answers "channels" (B), "channel_group" (G),
+ * "active" (channels not yet stopped), "shared_products" (batched product
+ * launches so far), "device_bytes" (A counted once), "symv" and "dense_exact"
+ * (as a session).
+ *
+ * PFDR_ERR_ARG, with the offence named by pfdr_last_error, before any device
+ * work and without a handle: B outside [1, 64]; N == 0 (an identity or
+ * diagonal A has no product to share: use one reusable session and
+ * pfdr_session_reload); the simplex kind; A == NULL; nranks > 1 or a
+ * communicator (a device group, pfdr_set_devices, does not apply either);
+ * anything pfdr_session_create refuses for one channel.  A sparse A is not
+ * offered here: there is no pfdr_csc argument. */
+typedef struct pfdr_batch pfdr_batch;
+int pfdr_batch_create(pfdr_batch **out, const pfdr_problem *p, int B);
+int pfdr_batch_run(pfdr_batch *b, int iters, int *it /* B, may be NULL */);
+int pfdr_batch_result(pfdr_batch *b, void *X, int *it, void *Obj, void *Dif);
+int pfdr_batch_reload(pfdr_batch *b, const pfdr_reload *r);
+int pfdr_batch_query(pfdr_batch *b, const char *what, int64_t *value);
+void pfdr_batch_destroy(pfdr_batch *b);
 
 /* ------------------------------------------- dense matrices (CP builder) -- */
 /* Gram matrix on the matrix cores (exact-f32 / f64 MFMA, fixed-order
